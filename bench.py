@@ -12,7 +12,14 @@ from cold buffers.  With N ranks the cells are split round-robin (3 per GPU at 8
 collective in the data path; value = 24 / (max over ranks of the seconds per sweep):
 STRONG scaling (the sweep's total work is fixed).
 
-Secondary legs on the same line (each its own object):
+A plain run (``python bench.py --gpus 1 --steps N --warmup W``) does only what the headline
+needs: set-up, W warm-up sweeps, the N timed sweeps, the result line.  ``--dump-outputs DIR``
+also writes what the last timed sweep returned (the StationaryResult arrays of all 24 cells)
+as DIR/<name>.npy, float64; the inputs are the fixed Table II calibrations, identical from
+run to run.  Everything else runs only with ``--full``: the secondary legs below (``--legs``
+selects among them) and the CPU baseline (unless ``--no-cpu-baseline``).
+
+Secondary legs on the same line (``--full``; each its own object):
   configs1  -- BASELINE configs[1]: the reference's own Krusell-Smith-form GE solve
                (Aiyagari-HARK.py:249) at 10 000 grid points x 1 000 006 agents x 11 000
                periods per GE iteration; one independent economy per rank.
@@ -70,6 +77,7 @@ C3_PANEL_TEMPLATE = "sim_resident_kernel<1024, 4, false, true"
 EGM_C1_TEMPLATE = "egm_cycle_kernel<32, 28, false, 2"
 C4_TEMPLATE = "hist_pull_kernel<32, 512"
 N_TABLE2_CPU_CELL = 6          # (rho 0.6, sigma 0.2, CRRA 1) in stationary.table2_calibrations() order
+SECONDARY_LEGS = ("configs1", "configs3", "configs4", "table2_reference")   # run only with --full
 
 
 def log(*a):
@@ -185,6 +193,31 @@ def hist_stats(h, reset, dev=None):
     return tot_ms, tot_n
 
 
+DUMP_FIELDS = ("r", "K", "K_supply", "KtoY", "saving_rate", "status")
+
+
+def dump_outputs(path, res, mine, n_cells, world, rank):
+    """--dump-outputs: every per-calibration array of the StationaryResult the last timed
+    sweep returned (what a caller of solve_table2 receives), put back in Table II cell order
+    over the ranks, one float64 DIR/<field>.npy of n_cells values each (status: the search's
+    flag bits as numbers).  Rank 0 writes.  The inputs never change, but the rebalancing stop
+    points follow the wall clock (r_note below), so two runs of one build agree to the search
+    tolerance, not bit for bit: measured between two runs, r within 2e-8 absolute (r_tol = 1e-7),
+    K / KtoY / saving_rate within 1.4e-7 relative, and K_supply (K_s at the last r evaluated, steep
+    in r) within 1.8e-4 relative."""
+    parts = gather_objects({f: np.asarray(getattr(res, f), dtype=np.float64) for f in DUMP_FIELDS}, world)
+    cells_of = gather_objects(list(mine), world)
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    for f in DUMP_FIELDS:
+        full = np.full(n_cells, np.nan)
+        for ii, part in zip(cells_of, parts):
+            full[ii] = part[f]
+        np.save(os.path.join(path, f + ".npy"), full)
+    log(f"[bench] wrote {', '.join(f + '.npy' for f in DUMP_FIELDS)} ({n_cells} cells each) to {path}")
+
+
 # ------------------------------------------------------------------------------------
 # headline: configs[2] Table II stationary sweep
 # ------------------------------------------------------------------------------------
@@ -245,6 +278,8 @@ def table2_leg(args, world, rank, dev):
     for pr in per_rank:
         for k, rr, ky in zip(pr["cells"], pr["r"], pr["KtoY"]):
             r[k], kty[k] = rr, ky
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, mine, len(cells), world, rank)
     out = dict(seconds_per_sweep=el / args.steps, value=len(cells) * args.steps / el, kernel=kern,
                resident=ge_n > 0, egm_cycles_per_sweep=ge_cyc / args.steps if ge_n else None,
                hist_kernel_ms_per_sweep=hist_ms / args.steps, hist_launches_per_sweep=hist_n / args.steps,
@@ -769,10 +804,15 @@ def main():
     ap.add_argument("--c3-agents", type=int, default=N_AGENTS_C3)
     ap.add_argument("--c3-periods", type=int, default=T_C3)
     ap.add_argument("--stress-grid", type=int, default=STRESS_N_A)
-    ap.add_argument("--legs", default="table2,configs1,configs3,configs4,table2_reference")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondary legs (--legs) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed sweep returned (all cells) as DIR/<name>.npy, float64")
+    ap.add_argument("--legs", default=None,
+                    help="with --full: the secondary legs to run (default " + ",".join(SECONDARY_LEGS) + ")")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="gloo: one-GPU rehearsal of the multi-rank run (every rank on device 0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--pmc-pass", action="store_true",
                     help="profiling pass (tools/prof_bench.sh): timed work only, [bench-alg] records on stderr")
     ap.add_argument("--hist-pull", type=int, default=None,
@@ -786,6 +826,14 @@ def main():
     ap.add_argument("--ge-loose-hist", type=int, default=None,
                     help="AIY_OPT_GE_LOOSE_HIST (loose-bracketing histogram tolerance 10^-v; default the library's)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    # the headline (table2) always runs; every other leg and the CPU baseline only with --full
+    legs = set((args.legs or ",".join(SECONDARY_LEGS)).split(",")) - {"table2"} if args.full or args.legs else set()
+    if legs - set(SECONDARY_LEGS):
+        ap.error("unknown leg(s) " + ",".join(sorted(legs - set(SECONDARY_LEGS))))
+    if legs and not args.full:
+        ap.error("--legs " + ",".join(sorted(legs)) + " needs --full (a plain run times the Table II sweep only)")
     global PMC_PASS
     PMC_PASS = args.pmc_pass
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -800,7 +848,6 @@ def main():
     if rank == 0:
         build.build(verbose=False)
     barrier(world)
-    legs = set(args.legs.split(","))
     if (args.hist_pull is not None or args.ge_rebalance is not None or args.ge_loose_hist is not None or
             args.hist_cluster is not None or args.ge_anderson is not None):
         from aiyagari_hark_amd import _lib
@@ -885,7 +932,7 @@ def main():
         line["configs4"] = configs4_leg(args, world, rank, dev)
     if "table2_reference" in legs:
         line["table2_reference"] = table2_reference_leg(world, rank, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         ks_iters = line.get("table2_reference", {}).get("ge_iterations_rank0")
         line["cpu_baseline"] = cpu_baseline(args.grid, t2["r_percent"][N_TABLE2_CPU_CELL] / 100.0,
                                             ks_ge_iterations=ks_iters)

@@ -249,8 +249,8 @@ def test_configs3_fullsize_two_step_shards_match_oracle(c3, gpu):
 def _bench_line(extra, timeout):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-           "--legs", "table2,configs3", "--grid", "2000", "--c3-agents", "2100000", "--c3-periods", "40"] + extra
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--legs", "table2,configs3", "--grid", "2000", "--c3-agents", "2100000", "--c3-periods", "40"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     sys.stderr.write(out.stderr[-3000:])
     assert out.returncode == 0, out.stderr[-3000:]

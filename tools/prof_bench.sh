@@ -26,7 +26,7 @@ d = dict(source_digest=build.source_digest(), lib_digest=build.library_digest(li
          lib_mtime=os.path.getmtime(lib), git_head='$head'); \
 assert d['lib_digest'] == d['source_digest'], ('stale library', d); \
 json.dump(d, open('$out/stamp_$stage.json', 'w'))" || exit 3
-B="bench.py --steps 1 --warmup 0 --no-cpu-baseline --pmc-pass --legs $legs"
+B="bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --pmc-pass --legs $legs"
 case $stage in
   trace)
     timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- python3 $B > $out/trace.log 2>&1 ;;
