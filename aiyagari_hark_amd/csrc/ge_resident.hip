@@ -163,74 +163,15 @@ struct GeState {
 };
 
 // Cluster-wide reduction of nv per-thread values (bit v of kmax: NaN-propagating max, else
-// sum) in a fixed order at every level, through tagged 8-byte granules (hist_bicg.h's
-// protocol; every workgroup computes the same s_res).  It is also a barrier: every
-// workgroup has published after all its waves drained their stores.
+// sum) by hist_cluster.h's hc_reduce (every workgroup computes the same s_res), on the granules
+// and the epoch counter the BiCGSTAB solves of the same launch use.  It is also a barrier:
+// every workgroup has published after all its waves drained their stores.
 template <int TH>
 __device__ __forceinline__ bool ge_reduce(unsigned long long* gran, int G, int w, unsigned& ne, const double* vals,
                                           int nv, unsigned kmax, double (*s_part)[kGeWavesMax], double* s_res,
                                           int* s_flag, unsigned* err) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  for (int v = 0; v < nv; ++v) {
-    const double x = (kmax >> v) & 1u ? wave_nan_max(vals[v]) : wave_sum_lane63(vals[v]);
-    if (lane == kWave - 1) s_part[v][wid] = x;
-  }
-  __syncthreads();
-  ++ne;
-  const unsigned long long tag = (unsigned long long)ne << 32;
-  unsigned long long* slot = gran + (size_t)(ne & 1) * G * kHcRedRec;
-  if (tid < nv) {
-    const int v = tid;
-    double x = s_part[v][0];
-    for (int q = 1; q < TH / kWave; ++q) x = (kmax >> v) & 1u ? nan_max(x, s_part[v][q]) : x + s_part[v][q];
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    unsigned long long* g = slot + (size_t)w * kHcRedRec + 2 * v;
-    __hip_atomic_store(to_global(g), tag | (b >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(to_global(g + 1), tag | (b & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (wid == 0) {
-    double xa[kHkRed], xb[kHkRed];
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    bool ok;
-    do {
-      ok = true;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int w2 = lane + u * kWave;
-#pragma unroll
-        for (int v = 0; v < kHkRed; ++v) {
-          double x = 0.0;
-          if (v < nv && w2 < G) {
-            const unsigned long long* g = slot + (size_t)w2 * kHcRedRec + 2 * v;
-            const unsigned long long hi = __hip_atomic_load(to_global(g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long lo = __hip_atomic_load(to_global(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = ok && (hi & 0xffffffff00000000ull) == tag && (lo & 0xffffffff00000000ull) == tag;
-            x = __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull)));
-          }
-          if (u == 0) xa[v] = x;
-          else xb[v] = x;
-        }
-      }
-      if (__all(ok)) break;
-      __builtin_amdgcn_s_sleep(1);
-      if (__builtin_amdgcn_s_memrealtime() - t0 > kHcTimeoutTicks) {
-        if (lane == 0) __hip_atomic_store(to_global(err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-    } while (true);
-    if (lane == 0) *s_flag = ok ? 1 : 0;
-#pragma unroll
-    for (int v = 0; v < kHkRed; ++v) {
-      if (v < nv) {
-        const bool mx = (kmax >> v) & 1u;
-        const double y = mx ? wave_nan_max(nan_max(xa[v], xb[v])) : wave_sum_lane63(xa[v] + xb[v]);
-        if (lane == kWave - 1) s_res[v] = y;
-      }
-    }
-  }
-  __syncthreads();
-  return *s_flag != 0;
+  return hc_reduce<TH>(gran, G, w, ne, vals, nv, kmax, s_part, s_res, s_flag, err, [] {});
 }
 
 // Interpolation pass over the workgroup's own asset columns, one 64-column tile per wave at
@@ -404,8 +345,8 @@ __device__ __forceinline__ double ge_egm_cycle(int S, int n_a, int j0, int j1, c
 // own non-inlined functions, each with its own register allocation) address it directly.
 constexpr int kGeSmax = 8;    // the largest resident state count (Table II: 7)
 extern __shared__ double ge_dyn[];                 // histogram: span buffer + v; EGM: V tiles + windows
-__shared__ double ge_s_part[kHkRed][kGeWavesMax];
-__shared__ double ge_s_res[kHkRed];
+__shared__ double ge_s_part[kHcRed][kGeWavesMax];
+__shared__ double ge_s_res[kHcRed];
 __shared__ int ge_s_flag;
 __shared__ double ge_s_Pe[kGeSmax * kGeSmax];     // P[s][s'] unpadded (egm_phase2's layout)
 __shared__ double ge_s_Wl[kGeSmax];               // w l(s')
@@ -981,7 +922,7 @@ static bool ge_make_plan(aiy_handle* h, int n_cal, int S, int n_a, GePlan& p) {
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) return false;
   if (h->cu_limit > 0) cus = std::min(cus, h->cu_limit);
   const int g_min = (n_a + 2 * 512 - 1) / (2 * 512);
-  // the cluster reductions (ge_reduce, hist_bicg.h) read at most kHcMaxG workgroups
+  // the cluster reductions' sweep (hc_sweep, hist_cluster.h) reads at most kHcMaxG workgroups
   if (g_min > kHcMaxG || g_min > cus) return false;
   const int g_cap = h->hist_cluster_cap > 0 ? h->hist_cluster_cap : 32;
   int G = std::max(g_min, std::min(std::min(g_cap, kHcMaxG), cus / n_cal));

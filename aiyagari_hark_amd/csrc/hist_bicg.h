@@ -9,10 +9,8 @@
 
 namespace aiy {
 
-constexpr int kHkRed = 8;   // partial sums per reduction (at most)
 constexpr int kHkStall = 256;   // matvecs without a 10 % residual gain that count as a stall
 constexpr double kHkStopSentinel = 1e300;   // rebalancing stop request on the max|r| partial
-static_assert(2 * kHkRed <= kHcRedRec, "two granules per partial sum");
 // Destinations covered by more than two spans (the borrowing constraint, the top of the grid:
 // up to kHcCand covering workgroups) are summed by a whole wave, one candidate per lane, instead
 // of a serial per-lane loop whose dependent slab loads put the owning workgroup ~2 us behind the
@@ -87,8 +85,8 @@ struct HkShared {
   int* s_ncand;                    // [SMAX]
   unsigned short* s_cinfo;         // [KC SMAX TH]
   double* s_P;                     // [SMAX SMAX]
-  double (*s_part)[TH / kWave];    // [kHkRed]
-  double* s_res;                   // [kHkRed]
+  double (*s_part)[TH / kWave];    // [kHcRed]
+  double* s_res;                   // [kHcRed]
   int* s_flag;
   int* s_stop;
   int* s_ex;                       // [SMAX][2] pull form: exported prefix / suffix of the own sources
@@ -186,10 +184,6 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   int* s_ex = L.s_ex;
   int* Ainv = (int*)r.Ainv;
   double* Qg = (double*)r.Qg;
-  auto lo_at = [&](int s, int j) -> int {
-    const int* p = LO + (size_t)s * n_a + j;
-    return r.lottery_fresh ? __hip_atomic_load(to_global(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-  };
   if constexpr (PULL) {
     const int n1 = n_a + 1;
     unsigned bad = 0u;
@@ -201,8 +195,8 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     }
     for (int q = tid; q < S * n_own; q += TH) {
       const int s = q / n_own, j = j0 + (q - s * n_own);
-      const int l = lo_at(s, j);
-      const int lp = j > 0 ? lo_at(s, j - 1) : -1;
+      const int l = hc_lo_at(LO, n_a, r.lottery_fresh, s, j);
+      const int lp = j > 0 ? hc_lo_at(LO, n_a, r.lottery_fresh, s, j - 1) : -1;
       // only a monotone lottery inside the grid is scattered (anything else: error 2, the
       // caller falls back); the loops never index outside the row
       const bool ok = l >= 0 && l <= n_a - 2 && lp >= -1 && lp <= l;
@@ -218,26 +212,10 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     }
     if (S * aspan * (int)sizeof(int) > cap * (int)sizeof(double)) bad = 2u;
     if (bad) __hip_atomic_store(to_global(err), bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < S) {   // exported prefix [j0, ex0) (lo < j0) and suffix [ex1, j1) (lo + 1 >= j1)
-      const int s = tid;
-      int lo = j0, hi = j1;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (lo_at(s, mid) < j0) lo = mid + 1; else hi = mid;
-      }
-      s_ex[2 * s] = lo;
-      int lo2 = j0, hi2 = j1;
-      while (lo2 < hi2) {
-        const int mid = (lo2 + hi2) >> 1;
-        if (lo_at(s, mid) + 1 < j1) lo2 = mid + 1; else hi2 = mid;
-      }
-      s_ex[2 * s + 1] = lo2;
-    }
+    hc_exported(LO, n_a, r.lottery_fresh, S, j0, j1, s_ex);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (!barrier()) return -1;
-    if (tid == 0) s_stop = __hip_atomic_load(to_global(err), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-    __syncthreads();
-    if (s_stop) return -1;
+    if (hc_failed(err, &s_stop)) return -1;
     for (int q = tid; q < S * aspan; q += TH) {   // A(d) for d in [j0 - 1, j1] (A(-1) = 0)
       const int s = q / aspan, d = j0 - 1 + (q - s * aspan);
       s_A[q] = d < 0 ? 0 : __hip_atomic_load(to_global(&Ainv[(size_t)s * n1 + d]), __ATOMIC_RELAXED,
@@ -272,9 +250,7 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   }
   if (!PULL) {
   if (!barrier()) return -1;
-  if (tid == 0) s_stop = __hip_atomic_load(to_global(err), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-  __syncthreads();
-  if (s_stop) return -1;
+  if (hc_failed(err, &s_stop)) return -1;
   if (tid < S) {
     const int s = tid;
     int n = 0, bad = 0;
@@ -298,9 +274,7 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   const int total = s_tot;
   for (int q = tid; q < total; q += TH) Tacc[q] = 0.0;
   if (!barrier()) return -1;
-  if (tid == 0) s_stop = __hip_atomic_load(to_global(err), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-  __syncthreads();
-  if (s_stop) return -1;
+  if (hc_failed(err, &s_stop)) return -1;
   }   // !PULL setup
 #pragma unroll
   for (int k = 0; k < KC; ++k) {
@@ -712,111 +686,38 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     HK_PH(3);
     return true;
   };
-  // cluster-wide reduction of NV per-thread partials (bit v of kmax: nan_max, else sum),
-  // fixed order at every level, so every workgroup gets the same s_res
-  // cluster-wide reduction of NV per-thread partials (bit v of kmax: nan_max, else sum),
-  // fixed order at every level, so every workgroup gets the same s_res.  The workgroup's
-  // values travel as tagged 8-byte granules ({epoch, 32 data bits}, two per double, sc1
-  // stores; MI355X_MICROARCH.md hand-off R2): the data is its own flag, so there is no
-  // counter barrier and no store drain -- wave 0 re-reads the cluster's granules until
-  // every tag carries this reduction's epoch.  Epochs count up from 1 within a launch (the
-  // host zeroes the granules before each launch); slots alternate by epoch parity, and a
-  // matvec barrier separates any two reductions, so a slot is rewritten only after every
-  // workgroup has read it.
-  // the workgroup's wave partials of nv values into s_part (visible after the next barrier)
-  auto wave_parts = [&](const double* vals, int nv, unsigned kmax) {
-#pragma unroll
-    for (int v = 0; v < kHkRed; ++v) {
-      if (v < nv) {
-        const double x = (kmax >> v) & 1u ? wave_nan_max(vals[v]) : wave_sum_lane63(vals[v]);
-        if (lane == kWave - 1) s_part[v][wid] = x;
-      }
-    }
-  };
-  // threads < nv: the workgroup's values (waves in fixed order) as two tagged granules each
-  auto store_granules = [&](unsigned long long* slot, unsigned long long tag, int nv, unsigned kmax) {
-    if (tid < nv) {
-      const int v = tid;
-      double x = s_part[v][0];
-      for (int q = 1; q < TH / kWave; ++q) x = (kmax >> v) & 1u ? nan_max(x, s_part[v][q]) : x + s_part[v][q];
-      const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-      unsigned long long* g = slot + (size_t)w * (2 * kHkRed) + 2 * v;
-      __hip_atomic_store(to_global(g), tag | (b >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(to_global(g + 1), tag | (b & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  };
-  // wave 0: every workgroup's granules (until every tag carries this epoch), fixed-order sums
-  // into s_res; *s_ok = 0 on timeout (error word set)
-  auto sweep = [&](const unsigned long long* slot, unsigned long long tag, int nv, unsigned kmax, int* s_ok) {
-    {
-      double xa[kHkRed], xb[kHkRed];
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      bool ok;
-      do {   // every granule load of a pass in flight before the tag test
-        ok = true;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int w2 = lane + u * kWave;
-#pragma unroll
-          for (int v = 0; v < kHkRed; ++v) {
-            double x = 0.0;
-            if (v < nv && w2 < G) {
-              const unsigned long long* g = slot + (size_t)w2 * (2 * kHkRed) + 2 * v;
-              const unsigned long long hi = __hip_atomic_load(to_global(g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              const unsigned long long lo = __hip_atomic_load(to_global(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              ok = ok && (hi & 0xffffffff00000000ull) == tag && (lo & 0xffffffff00000000ull) == tag;
-              x = __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull)));
-            }
-            if (u == 0) xa[v] = x;
-            else xb[v] = x;
-          }
-        }
-        if (__all(ok)) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (__builtin_amdgcn_s_memrealtime() - t0 > kHcTimeoutTicks) {
-          if (lane == 0) __hip_atomic_store(to_global(err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-      } while (true);
-      if (lane == 0) *s_ok = ok ? 1 : 0;
-#pragma unroll
-      for (int v = 0; v < kHkRed; ++v) {
-        if (v < nv) {
-          const bool mx = (kmax >> v) & 1u;
-          const double y = mx ? wave_nan_max(nan_max(xa[v], xb[v])) : wave_sum_lane63(xa[v] + xb[v]);
-          if (lane == kWave - 1) s_res[v] = y;
-        }
-      }
-    }
-  };
-  auto reduce = [&](double (&vals)[kHkRed], int nv, unsigned kmax, auto&& prefetch) -> bool {
+  // cluster-wide reduction of nv per-thread partials into s_res (hist_cluster.h's protocol);
+  // prefetch(): loads the step after the reduction needs, in flight across the sweep.
+  // hc_reduce's steps written out: through hc_reduce, with prefetch handed on as its hook, the
+  // two-column push kernel (hist_bicg_kernel<8, 2, 512, false>) spilled 4 bytes per lane more
+  auto reduce = [&](double (&vals)[kHcRed], int nv, unsigned kmax, auto&& prefetch) -> bool {
     HK_PH(5);
-    wave_parts(vals, nv, kmax);
+    hc_wave_parts(vals, nv, kmax, s_part);
     __syncthreads();
     ++ne;
-    const unsigned long long tag = (unsigned long long)ne << 32;
-    unsigned long long* slot = gran + (size_t)(ne & 1) * G * (2 * kHkRed);
-    store_granules(slot, tag, nv, kmax);
-    prefetch();   // loads the step after the reduction needs, in flight across the sweep
-    if (wid == 0) sweep(slot, tag, nv, kmax, &s_flag);
+    const unsigned long long tag = hc_red_tag(ne);
+    unsigned long long* slot = hc_red_slot(gran, G, ne);
+    hc_store_granules<TH>(slot, w, tag, nv, kmax, s_part);
+    prefetch();
+    if (wid == 0) hc_sweep(slot, G, tag, nv, kmax, s_res, &s_flag, err);
     __syncthreads();
     HK_PH(4);
     return s_flag != 0;
   };
   // one matvec out = T q whose cluster barrier also carries a reduction of nv values computed
   // before it (pipelined BiCGSTAB): the granules are stored before the publish's store drain,
-  // so every workgroup's are in memory once the barrier has passed; wave 0 reads them while
-  // the other waves gather, and s_res is valid on return
+  // so every workgroup's are in memory once the barrier has passed; the last wave reads them
+  // while the other waves gather, and s_res is valid on return
   // do_push(): the push of the matvec input (ends with a workgroup barrier)
   auto matvec_rp = [&](auto&& do_push, double (&out)[KC][SMAX], const double* vals, int nv, unsigned kmax) -> bool {
     HK_PH(5);
-    wave_parts(vals, nv, kmax);
+    hc_wave_parts(vals, nv, kmax, s_part);
     do_push();   // ends with a workgroup barrier: s_part complete
     HK_PH(0);
     ++ne;
-    const unsigned long long tag = (unsigned long long)ne << 32;
-    unsigned long long* slot = gran + (size_t)(ne & 1) * G * (2 * kHkRed);
-    store_granules(slot, tag, nv, kmax);
+    const unsigned long long tag = hc_red_tag(ne);
+    unsigned long long* slot = hc_red_slot(gran, G, ne);
+    hc_store_granules<TH>(slot, w, tag, nv, kmax, s_part);
     const int par = (int)((nb + 1) & 1);
     publish(par);   // every thread's s_waitcnt vmcnt(0): slabs and granules drained
     HK_PH(1);
@@ -824,7 +725,7 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     HK_PH(2);
     // the sweep by the last wave: with one column per thread its lanes own no columns whenever
     // a workgroup has <= TH - 64 of them (G >= 23 at N_a = 10 000), so it overlaps the gather
-    if (wid == TH / kWave - 1) sweep(slot, tag, nv, kmax, L.s_rok);
+    if (wid == TH / kWave - 1) hc_sweep(slot, G, tag, nv, kmax, s_res, L.s_rok, err);
     gather_mix(par, out);
     __syncthreads();
     HK_PH(3);
@@ -841,7 +742,7 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   double* Vl = kVlds ? Tacc + cap : (double*)r.Vg;
   double* Pg = (double*)r.Pg;
   auto vidx = [&](int k, int s) { return (k * SMAX + s) * TH + tid; };
-  double part[kHkRed];
+  double part[kHcRed];
   const double tol = r.tol;
   int mv = 0;                 // matvecs
   bool restart = true, first = true;
@@ -1162,8 +1063,8 @@ __device__ __forceinline__ int hk_solve_inlined(HkArgs a, unsigned* nb_io, unsig
   __shared__ int s_ncand[SMAX];
   __shared__ unsigned short s_cinfo[PULL ? 1 : KC * SMAX * TH];
   __shared__ double s_P[SMAX * SMAX];
-  __shared__ double s_part[kHkRed][TH / kWave];
-  __shared__ double s_res[kHkRed];
+  __shared__ double s_part[kHcRed][TH / kWave];
+  __shared__ double s_res[kHcRed];
   __shared__ int s_flag, s_stop;
   __shared__ int s_ex[2 * SMAX];
   __shared__ int s_nheavy, s_heavy[kHkHeavy][4], s_rok, s_wcnt[TH / kWave];
@@ -1186,8 +1087,8 @@ __device__ __noinline__ int hk_solve_isolated(HkArgs a, unsigned* nb_io, unsigne
   __shared__ int s_ncand[SMAX];
   __shared__ unsigned short s_cinfo[KC * SMAX * TH];
   __shared__ double s_P[SMAX * SMAX];
-  __shared__ double s_part[kHkRed][TH / kWave];
-  __shared__ double s_res[kHkRed];
+  __shared__ double s_part[kHcRed][TH / kWave];
+  __shared__ double s_res[kHcRed];
   __shared__ int s_flag, s_stop;
   __shared__ int s_ex[2 * SMAX];
   __shared__ int s_nheavy, s_heavy[kHkHeavy][4], s_rok, s_wcnt[TH / kWave];

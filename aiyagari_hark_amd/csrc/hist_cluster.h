@@ -1,6 +1,10 @@
-// Shared pieces of the device-resident distribution-iteration kernels (hist_resident.hip:
-// plain / Aitken iteration; hist_krylov.hip: BiCGSTAB): the per-calibration cluster run
-// description, the covering-span record, the cluster barrier and wave sums.
+// Shared pieces of the kernels in which a calibration's cluster of workgroups works on one
+// stationary distribution (hist_resident.hip: plain / Aitken iteration; hist_krylov.hip:
+// BiCGSTAB, push form hist_bicg.h and pull form hist_pull.h; ge_resident.hip: the whole GE
+// search): the per-calibration cluster run description, the covering-span record, the
+// cluster barriers, wave sums, the cluster reduction (hc_reduce and its pieces: the one
+// definition every BiCGSTAB solve and the GE search run) and the pull forms' exported
+// prefix / suffix search.
 #pragma once
 
 #include "common.h"
@@ -17,8 +21,10 @@ struct HcGather {
 };
 constexpr size_t kHcLdsTotal = 160 * 1024;         // per CU
 constexpr unsigned long long kHcTimeoutTicks = 200000000ull;   // 2 s of the 100 MHz clock
-constexpr int kHcCtrStride = 32;
-constexpr int kHcRedRec = 16;                     // 8-byte words per (parity, workgroup) record of `dist`                   // uints between cluster counters (128 B)
+constexpr int kHcCtrStride = 32;                   // uints between cluster counters (128 B)
+constexpr int kHcRedRec = 16;                      // 8-byte words per (parity, workgroup) record of `dist`
+constexpr int kHcRed = 8;                          // values per cluster reduction (at most)
+static_assert(2 * kHcRed <= kHcRedRec, "two granules per value of a reduction");
 
 struct HcRun {
   int n_cal, cal0, S, n_a, G, nj, cap;   // cap: doubles of the span buffer / one slab
@@ -135,6 +141,150 @@ __device__ __forceinline__ double wave_sum_lane63(double v) {
   v += dpp_add_src<0x142, 0xA>(v);   // row_bcast:15 into rows 1, 3
   v += dpp_add_src<0x143, 0xC>(v);   // row_bcast:31 into rows 2, 3
   return v;
+}
+
+// Whether the cluster's error word is set: thread 0 reads it, every thread gets the answer.
+// Called behind a cluster barrier, so every workgroup of the cluster gets the same one.
+__device__ __forceinline__ bool hc_failed(const unsigned* err, int* s_stop) {
+  if (threadIdx.x == 0) *s_stop = __hip_atomic_load(to_global(err), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+  __syncthreads();
+  return *s_stop != 0;
+}
+
+// ---- cluster reduction ----
+// Cluster-wide reduction of nv <= kHcRed per-thread values (bit v of kmax: nan_max, else sum),
+// fixed order at every level, so every workgroup gets the same s_res: lanes by
+// wave_sum_lane63 / wave_nan_max, waves ascending, then workgroups lane and lane + 64 and the
+// wave sum over lanes.  The workgroup's values travel as tagged 8-byte granules ({epoch, 32
+// data bits}, two per double, sc1 stores; MI355X_MICROARCH.md hand-off R2): the data is its
+// own flag, so there is no counter barrier and no store drain -- one wave re-reads the
+// cluster's granules until every tag carries this reduction's epoch.  Epochs count up from 1
+// within a launch (the host zeroes the granules before each launch) and every user of a
+// launch counts on the same `ne`; slots alternate by epoch parity, and a workgroup stores
+// epoch e + 1 only after its sweep of epoch e, so when a slot is rewritten (epoch e + 2, after
+// a sweep that saw every workgroup's e + 1) every workgroup has read it.
+__device__ __forceinline__ unsigned long long hc_red_tag(unsigned ne) { return (unsigned long long)ne << 32; }
+__device__ __forceinline__ unsigned long long* hc_red_slot(unsigned long long* gran, int G, unsigned ne) {
+  return gran + (size_t)(ne & 1) * G * kHcRedRec;
+}
+// the workgroup's wave partials of nv values into s_part (visible after the next barrier)
+template <int NWS>
+__device__ __forceinline__ void hc_wave_parts(const double* vals, int nv, unsigned kmax, double (*s_part)[NWS]) {
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+#pragma unroll
+  for (int v = 0; v < kHcRed; ++v) {
+    if (v < nv) {
+      const double x = (kmax >> v) & 1u ? wave_nan_max(vals[v]) : wave_sum_lane63(vals[v]);
+      if (lane == kWave - 1) s_part[v][wid] = x;
+    }
+  }
+}
+// threads < nv: workgroup w's values (its TH / kWave waves in ascending order) as two tagged
+// granules each
+template <int TH, int NWS>
+__device__ __forceinline__ void hc_store_granules(unsigned long long* slot, int w, unsigned long long tag, int nv,
+                                                  unsigned kmax, double (*s_part)[NWS]) {
+  const int tid = threadIdx.x;
+  if (tid < nv) {
+    const int v = tid;
+    double x = s_part[v][0];
+    for (int q = 1; q < TH / kWave; ++q) x = (kmax >> v) & 1u ? nan_max(x, s_part[v][q]) : x + s_part[v][q];
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    unsigned long long* g = slot + (size_t)w * kHcRedRec + 2 * v;
+    __hip_atomic_store(to_global(g), tag | (b >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(to_global(g + 1), tag | (b & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// ONE wave: the granules of the cluster's G <= kHcMaxG workgroups (lanes read workgroups lane
+// and lane + 64, until every tag carries this epoch), fixed-order sums into s_res; *s_ok = 0
+// on timeout (error word set)
+__device__ __forceinline__ void hc_sweep(const unsigned long long* slot, int G, unsigned long long tag, int nv,
+                                         unsigned kmax, double* s_res, int* s_ok, unsigned* err) {
+  static_assert(kHcMaxG <= 2 * kWave, "two workgroups per lane of the sweeping wave");
+  const int lane = threadIdx.x & (kWave - 1);
+  double xa[kHcRed], xb[kHcRed];
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  bool ok;
+  do {   // every granule load of a pass in flight before the tag test
+    ok = true;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int w2 = lane + u * kWave;
+#pragma unroll
+      for (int v = 0; v < kHcRed; ++v) {
+        double x = 0.0;
+        if (v < nv && w2 < G) {
+          const unsigned long long* g = slot + (size_t)w2 * kHcRedRec + 2 * v;
+          const unsigned long long hi = __hip_atomic_load(to_global(g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const unsigned long long lo = __hip_atomic_load(to_global(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          ok = ok && (hi & 0xffffffff00000000ull) == tag && (lo & 0xffffffff00000000ull) == tag;
+          x = __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull)));
+        }
+        if (u == 0) xa[v] = x;
+        else xb[v] = x;
+      }
+    }
+    if (__all(ok)) break;
+    __builtin_amdgcn_s_sleep(1);
+    if (__builtin_amdgcn_s_memrealtime() - t0 > kHcTimeoutTicks) {
+      if (lane == 0) __hip_atomic_store(to_global(err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      break;
+    }
+  } while (true);
+  if (lane == 0) *s_ok = ok ? 1 : 0;
+#pragma unroll
+  for (int v = 0; v < kHcRed; ++v) {
+    if (v < nv) {
+      const bool mx = (kmax >> v) & 1u;
+      const double y = mx ? wave_nan_max(nan_max(xa[v], xb[v])) : wave_sum_lane63(xa[v] + xb[v]);
+      if (lane == kWave - 1) s_res[v] = y;
+    }
+  }
+}
+// The whole reduction by workgroup w of G (TH threads; NWS >= TH / kWave: the row length of
+// s_part): s_res valid in every thread on return, false on timeout.  prefetch(): loads the
+// step after the reduction needs, in flight across the sweep.
+template <int TH, int NWS, typename Prefetch>
+__device__ __forceinline__ bool hc_reduce(unsigned long long* gran, int G, int w, unsigned& ne, const double* vals,
+                                          int nv, unsigned kmax, double (*s_part)[NWS], double* s_res, int* s_flag,
+                                          unsigned* err, Prefetch&& prefetch) {
+  static_assert(TH / kWave <= NWS, "a partial per wave");
+  hc_wave_parts(vals, nv, kmax, s_part);
+  __syncthreads();
+  ++ne;
+  const unsigned long long tag = hc_red_tag(ne);
+  unsigned long long* slot = hc_red_slot(gran, G, ne);
+  hc_store_granules<TH>(slot, w, tag, nv, kmax, s_part);
+  prefetch();
+  if (threadIdx.x / kWave == 0) hc_sweep(slot, G, tag, nv, kmax, s_res, s_flag, err);
+  __syncthreads();
+  return *s_flag != 0;
+}
+
+// ---- pull forms: the lottery of the own sources ----
+// lottery index of source j of row s; fresh: written in this launch by other workgroups (sc1 load)
+__device__ __forceinline__ int hc_lo_at(const int* LO, int n_a, bool fresh, int s, int j) {
+  const int* p = LO + (size_t)s * n_a + j;
+  return fresh ? __hip_atomic_load(to_global(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
+}
+// threads < S: the exported prefix [j0, s_ex[2 s]) (lo < j0) and suffix [s_ex[2 s + 1], j1)
+// (lo + 1 >= j1) of row s's own sources [j0, j1), the ones other workgroups pull
+__device__ __forceinline__ void hc_exported(const int* LO, int n_a, bool fresh, int S, int j0, int j1, int* s_ex) {
+  if ((int)threadIdx.x < S) {
+    const int s = threadIdx.x;
+    int lo = j0, hi = j1;   // first own j with lo_j >= j0
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (hc_lo_at(LO, n_a, fresh, s, mid) < j0) lo = mid + 1; else hi = mid;
+    }
+    s_ex[2 * s] = lo;
+    int lo2 = j0, hi2 = j1;   // first own j with lo_j + 1 >= j1
+    while (lo2 < hi2) {
+      const int mid = (lo2 + hi2) >> 1;
+      if (hc_lo_at(LO, n_a, fresh, s, mid) + 1 < j1) lo2 = mid + 1; else hi2 = mid;
+    }
+    s_ex[2 * s + 1] = lo2;
+  }
 }
 
 // BiCGSTAB form of the cluster kernel (hist_krylov.hip) for (S, padded S, columns per

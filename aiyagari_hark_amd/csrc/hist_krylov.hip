@@ -50,8 +50,8 @@ __global__ __launch_bounds__(TH) void hist_bicg_kernel(HcRun r) {
   __shared__ int s_ncand[SMAX];
   __shared__ unsigned short s_cinfo[KC * SMAX * TH];   // hk_cinfo(cf, cn, heavy index)
   __shared__ double s_P[SMAX * SMAX];
-  __shared__ double s_part[kHkRed][TH / kWave];
-  __shared__ double s_res[kHkRed];
+  __shared__ double s_part[kHcRed][TH / kWave];
+  __shared__ double s_res[kHcRed];
   __shared__ int s_flag, s_stop;
   __shared__ int s_ex[2 * SMAX];
   __shared__ int s_nheavy, s_heavy[kHkHeavy][4], s_rok, s_wcnt[TH / kWave];
@@ -97,8 +97,8 @@ __global__ __launch_bounds__(TH) void hist_pull_kernel(HcRun r) {
   extern __shared__ int hp_dyn[];   // staged inverse lottery
   __shared__ double s_P[SMAX * SMAX];
   __shared__ int s_ex[2 * SMAX];
-  __shared__ double s_part[kHkRed][TH / kWave];
-  __shared__ double s_res[kHkRed];
+  __shared__ double s_part[kHcRed][TH / kWave];
+  __shared__ double s_res[kHcRed];
   __shared__ int s_flag, s_stop;
   const HpShared<SMAX, TH> L{s_P, hp_dyn, s_ex, s_part, s_res, &s_flag, &s_stop};
   const int G = r.G, S = r.S, n_a = r.n_a;

@@ -67,8 +67,8 @@ struct HpShared {
   double* s_P;                     // [SMAX][SMAX]
   int* s_A;                        // [SMAX][span]
   int* s_ex;                       // [SMAX][2]
-  double (*s_part)[TH / kWave];    // [kHkRed]
-  double* s_res;                   // [kHkRed]
+  double (*s_part)[TH / kWave];    // [kHcRed]
+  double* s_res;                   // [kHcRed]
   int* s_flag;
   int* s_stop;
 };
@@ -83,7 +83,7 @@ __host__ __device__ constexpr size_t hp_lds_bytes(int S, int n_own, int cw) {
 // non-monotone lottery), or -(2 + matvecs) on a rebalancing stop (X holds the iterate).
 template <int SMAX, int TH>
 __device__ __forceinline__ int hp_solve(const HpArgs& r, const HpShared<SMAX, TH>& L, unsigned& nb, unsigned& ne) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
   const int G = r.G, S = r.S, n_a = r.n_a, w = r.w, j0 = r.j0, j1 = r.j1;
   const int n_own = j1 - j0, span = n_own + 2;
   const int* LO = (const int*)r.LO;
@@ -131,10 +131,6 @@ __device__ __forceinline__ int hp_solve(const HpArgs& r, const HpShared<SMAX, TH
     ++nb;
     return hc_barrier(err, ctr, (unsigned)G * nb, &s_flag);
   };
-  auto lo_at = [&](int s, int j) -> int {
-    const int* p = LO + (size_t)s * n_a + j;
-    return r.lottery_fresh ? __hip_atomic_load(to_global(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-  };
 
   // ---- setup: P; inverse lottery scatter of the own sources; exported bounds ----
   for (int q = tid; q < SMAX * SMAX; q += TH) {
@@ -170,8 +166,8 @@ __device__ __forceinline__ int hp_solve(const HpArgs& r, const HpShared<SMAX, TH
     if (q < S * n_own) {
       s = q / n_own;
       const int j = j0 + (q - s * n_own);
-      const int l = lo_at(s, j);
-      const int lp = j > 0 ? lo_at(s, j - 1) : -1;
+      const int l = hc_lo_at(LO, n_a, r.lottery_fresh, s, j);
+      const int lp = j > 0 ? hc_lo_at(LO, n_a, r.lottery_fresh, s, j - 1) : -1;
       // only a monotone lottery inside the grid is scattered (anything else: error 2, the caller
       // falls back); the runs never leave the row
       const bool ok = l >= 0 && l <= n_a - 2 && lp >= -1 && lp <= l;
@@ -191,26 +187,9 @@ __device__ __forceinline__ int hp_solve(const HpArgs& r, const HpShared<SMAX, TH
     fill_run(s, tb, te, n_a);
   }
   if (bad) __hip_atomic_store(to_global(err), bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // exported prefix [j0, ex0) (lo < j0) and suffix [ex1, j1) (lo + 1 >= j1) of each row
-  if (tid < S) {
-    const int s = tid;
-    int lo = j0, hi = j1;   // first own j with lo_j >= j0
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (lo_at(s, mid) < j0) lo = mid + 1; else hi = mid;
-    }
-    s_ex[2 * s] = lo;
-    int lo2 = j0, hi2 = j1;   // first own j with lo_j + 1 >= j1
-    while (lo2 < hi2) {
-      const int mid = (lo2 + hi2) >> 1;
-      if (lo_at(s, mid) + 1 < j1) lo2 = mid + 1; else hi2 = mid;
-    }
-    s_ex[2 * s + 1] = lo2;
-  }
+  hc_exported(LO, n_a, r.lottery_fresh, S, j0, j1, s_ex);
   if (!barrier()) return -1;
-  if (tid == 0) s_stop = __hip_atomic_load(to_global(err), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-  __syncthreads();
-  if (s_stop) return -1;
+  if (hc_failed(err, &s_stop)) return -1;
   for (int q = tid; q < S * span; q += TH) {   // A(d) for d in [j0 - 1, j1] (A(-1) = 0)
     const int s = q / span, d = j0 - 1 + (q - s * span);
     s_A[s * span + (d - j0 + 1)] =
@@ -376,74 +355,13 @@ __device__ __forceinline__ int hp_solve(const HpArgs& r, const HpShared<SMAX, TH
     HP_PH(0);
     return true;
   };
-  // cluster-wide reduction (hist_bicg.h's protocol: tagged granules, fixed order)
-  auto reduce = [&](double (&vals)[kHkRed], int nv, unsigned kmax) -> bool {
+  // cluster-wide reduction of nv per-thread partials into s_res (hist_cluster.h's protocol)
+  auto reduce = [&](double (&vals)[kHcRed], int nv, unsigned kmax) -> bool {
     HP_PH(3);
-#pragma unroll
-    for (int v = 0; v < kHkRed; ++v) {
-      if (v < nv) {
-        const double x = (kmax >> v) & 1u ? wave_nan_max(vals[v]) : wave_sum_lane63(vals[v]);
-        if (lane == kWave - 1) L.s_part[v][wid] = x;
-      }
-    }
-    __syncthreads();
-    ++ne;
-    const unsigned long long tag = (unsigned long long)ne << 32;
-    unsigned long long* slot = gran + (size_t)(ne & 1) * G * (2 * kHkRed);
-    if (tid < nv) {
-      const int v = tid;
-      double x = L.s_part[v][0];
-      for (int q = 1; q < TH / kWave; ++q) x = (kmax >> v) & 1u ? nan_max(x, L.s_part[v][q]) : x + L.s_part[v][q];
-      const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-      unsigned long long* g = slot + (size_t)w * (2 * kHkRed) + 2 * v;
-      __hip_atomic_store(to_global(g), tag | (b >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(to_global(g + 1), tag | (b & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (wid == 0) {
-      double xa[kHkRed], xb[kHkRed];
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      bool ok;
-      do {
-        ok = true;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int w2 = lane + u * kWave;
-#pragma unroll
-          for (int v = 0; v < kHkRed; ++v) {
-            double x = 0.0;
-            if (v < nv && w2 < G) {
-              const unsigned long long* g = slot + (size_t)w2 * (2 * kHkRed) + 2 * v;
-              const unsigned long long hi = __hip_atomic_load(to_global(g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              const unsigned long long lo = __hip_atomic_load(to_global(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              ok = ok && (hi & 0xffffffff00000000ull) == tag && (lo & 0xffffffff00000000ull) == tag;
-              x = __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull)));
-            }
-            if (u == 0) xa[v] = x;
-            else xb[v] = x;
-          }
-        }
-        if (__all(ok)) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (__builtin_amdgcn_s_memrealtime() - t0 > kHcTimeoutTicks) {
-          if (lane == 0) __hip_atomic_store(to_global(err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-      } while (true);
-      if (lane == 0) s_flag = ok ? 1 : 0;
-#pragma unroll
-      for (int v = 0; v < kHkRed; ++v) {
-        if (v < nv) {
-          const bool mx = (kmax >> v) & 1u;
-          const double y = mx ? wave_nan_max(nan_max(xa[v], xb[v])) : wave_sum_lane63(xa[v] + xb[v]);
-          if (lane == kWave - 1) L.s_res[v] = y;
-        }
-      }
-    }
-    __syncthreads();
+    const bool ok = hc_reduce<TH>(gran, G, w, ne, vals, nv, kmax, L.s_part, L.s_res, &s_flag, err, [] {});
     HP_PH(2);
-    return s_flag != 0;
+    return ok;
   };
-  // every own point once (elementwise updates between the matvecs)
   // every own point once (elementwise updates between the matvecs), UP points per thread at a
   // time: ld(g) -> the point's inputs for all UP points first, then st(s, j, g, inputs) (the
   // next points' loads are not hoisted past this point's stores otherwise)
@@ -474,7 +392,7 @@ __device__ __forceinline__ int hp_solve(const HpArgs& r, const HpShared<SMAX, TH
   };
 
   // ---- BiCGSTAB on (I - T) x = 0 (hist_bicg.h, the same recurrences and stopping rule) ----
-  double part[kHkRed];
+  double part[kHcRed];
   const double tol = r.tol;
   int mv = 0;
   bool restart = true, first = true;
