@@ -30,6 +30,7 @@
 //     non-negative double.
 #include "common.h"
 #include "egm_common.h"
+#include "ge_search.h"
 #include "internal.h"
 
 #include <algorithm>
@@ -676,12 +677,7 @@ __global__ __launch_bounds__(256) void egm_aa_gram_kernel(long long per, const d
 #pragma unroll
   for (int v = 0; v < 9; ++v) acc[v] = 0.0;
   for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < per; q += (long long)gridDim.x * blockDim.x) {
-    const double w0 = W[0][q], w1 = W[1][q], w2 = W[2][q], w3 = W[3][q], w4 = W[4][q];
-    const double g0 = w1 - w0, g1 = w2 - w1, g2 = w3 - w2, g3 = w4 - w3;
-    const double d0 = g1 - g0, d1 = g2 - g1, d2 = g3 - g2;
-    acc[0] += d0 * d0; acc[1] += d0 * d1; acc[2] += d0 * d2;
-    acc[3] += d1 * d1; acc[4] += d1 * d2; acc[5] += d2 * d2;
-    acc[6] += d0 * g3; acc[7] += d1 * g3; acc[8] += d2 * g3;
+    aa_gram_add(W[0][q], W[1][q], W[2][q], W[3][q], W[4][q], acc);
   }
   __shared__ double s_w[9][256 / kWave];
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
@@ -705,7 +701,7 @@ __global__ void egm_aa_mix_kernel(long long per, int n_a, const double* ring, lo
   const int cal = blockIdx.y;
   const double* g = gam + (size_t)cal * 4;
   if (g[3] == 0.0) return;   // this calibration is not mixed (converged, or a degenerate system)
-  const double c0g = g[0], c1g = g[1], c2g = g[2];
+  const double cg[3] = {g[0], g[1], g[2]};
   const double* W1 = ring + (size_t)((c0 + 1) % 5) * buf + (size_t)cal * per;
   const double* W2 = ring + (size_t)((c0 + 2) % 5) * buf + (size_t)cal * per;
   const double* W3 = ring + (size_t)((c0 + 3) % 5) * buf + (size_t)cal * per;
@@ -713,29 +709,10 @@ __global__ void egm_aa_mix_kernel(long long per, int n_a, const double* ring, lo
   for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < per; q += (long long)gridDim.x * blockDim.x) {
     const int j = (int)(q % (n_a + 1));
     if (j == 0) continue;   // the (1e-7, 1e-7) node
-    const double w1 = W1[q], w2 = W2[q], w3 = W3[q], w4 = W4[q];
-    const double cn = w4 - ((c0g * (w2 - w1) + c1g * (w3 - w2)) + c2g * (w4 - w3));
+    const double cn = aa_mix(cg, W1[q], W2[q], W3[q], W4[q]);
     out_c[(size_t)cal * per + q] = cn;
     out_m[(size_t)cal * per + q] = a_grid[(size_t)cal * n_a + j - 1] + cn;   // AS:1499
   }
-}
-
-// gamma of one calibration from its summed Gram entries (the resident search's Cholesky, same
-// regularisation); false: degenerate or non-finite (no mix)
-static bool egm_aa_solve(const double* gs, double* gam) {
-  double a00 = gs[0], a01 = gs[1], a02 = gs[2], a11 = gs[3], a12 = gs[4], a22 = gs[5];
-  const double b0 = gs[6], b1 = gs[7], b2 = gs[8];
-  const double reg = 1e-12 * (a00 + a11 + a22);
-  if (!(reg > 0.0)) return false;
-  a00 += reg; a11 += reg; a22 += reg;
-  const double l00 = std::sqrt(a00), l10 = a01 / l00, l20 = a02 / l00;
-  const double l11 = std::sqrt(a11 - l10 * l10), l21 = (a12 - l20 * l10) / l11;
-  const double l22 = std::sqrt(a22 - l20 * l20 - l21 * l21);
-  const double y0 = b0 / l00, y1 = (b1 - l10 * y0) / l11, y2 = (b2 - l20 * y0 - l21 * y1) / l22;
-  gam[2] = y2 / l22;
-  gam[1] = (y1 - l21 * gam[2]) / l11;
-  gam[0] = (y0 - l10 * gam[1] - l20 * gam[2]) / l00;
-  return std::isfinite(gam[0]) && std::isfinite(gam[1]) && std::isfinite(gam[2]);
 }
 
 int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_egm_inputs* in, double tol,
@@ -846,7 +823,7 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
             for (int v = 0; v < 9; ++v) gs[v] += h_part[((size_t)c * kEgmAaBlocks + b) * 9 + v];
           double* g = &h_gam[(size_t)c * 4];
           g[3] = 0.0;
-          if (mixable(c) && egm_aa_solve(gs, g)) {
+          if (mixable(c) && aa_solve(gs, g)) {
             g[3] = 1.0;
             moved[c] = 1;
             mix = true;
@@ -870,15 +847,11 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
           continue;
         }
         const unsigned long long* sl = h->h_dist + (size_t)c * kSlots;
-        const double d1 = slot_max(sl, L), d0 = slot_max(sl, L - 1);
-        const double lam = d1 / d0;
-        if (d1 > 100.0 * tol_of(c) && lam > 0.5 && lam < 0.999 && lam_prev[c] > 0.0 &&
-            std::fabs(lam - lam_prev[c]) < 0.2 * (1.0 - lam)) {
-          hf[c] = lam / (1.0 - lam);
+        hf[c] = egm_extrap_factor(slot_max(sl, L), slot_max(sl, L - 1), tol_of(c), L, lam_prev[c]);
+        if (hf[c] != 0.0) {
           moved[c] = 1;
           any = true;
         }
-        lam_prev[c] = lam;
       }
       if (any) {
         AIY_HIP(h, hipMemcpyAsync(df, hf, sizeof(double) * n_cal, hipMemcpyHostToDevice, st));

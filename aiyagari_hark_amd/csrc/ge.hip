@@ -130,29 +130,25 @@ extern "C" int32_t aiy_ge_stationary(aiy_handle* h, const aiy_stationary_model* 
   double* pmass = reinterpret_cast<double*>(base + L.pmass);
   double* d_th = reinterpret_cast<double*>(base + L.th);
   const long long tab_per = (long long)S * (n_a + 1), pts_per = (long long)S * n_a;
-  std::vector<double> r_cur(n_cal, 0.0), r_prev(n_cal, 0.0), theta(n_cal, 0.0);
-  // loose bracketing: per-calibration tolerances of this step, and the calibrations whose
-  // last (loose) evaluation was too close to the root to trust its sign
+  // loose bracketing: per-calibration tolerances of this step (GeEval::plan, ge_search.h)
   double* d_etol = reinterpret_cast<double*>(base + L.etol);
   double* d_htol = reinterpret_cast<double*>(base + L.htol);
-  std::vector<double> etol(n_cal, o->egm_tol), htol(n_cal, o->hist_tol);
-  std::vector<char> loose(n_cal, 0), refine(n_cal, 0), adapt(n_cal, 0);
-  std::vector<double> fmin_rel(n_cal, HUGE_VAL);   // smallest accepted |K_s - K_d| / K_d (ge_search.h)
+  std::vector<double> theta(n_cal, 0.0), etol(n_cal, o->egm_tol), htol(n_cal, o->hist_tol);
   const bool loose_on = o->loose_bracket && o->method == 1;
-  const double kLooseEgm = std::max(o->egm_tol, AIY_GE_LOOSE_EGM), kLooseHist = std::max(o->hist_tol, std::pow(10.0, -(double)h->ge_loose_hist));
+  const GeEvalOpts eo{o->method, o->loose_bracket != 0, h->ge_logsec, o->warm_egm != 0, o->warm_hist != 0,
+                      o->secant_start != 0, o->r_tol, o->egm_tol, o->hist_tol, std::pow(10.0, -(double)h->ge_loose_hist)};
   const unsigned sec_blocks = 1024;
   AIY_HIP(h, hipMemsetAsync(Mg, 0, sizeof(double) * n_cal, st));
 
   std::vector<int32_t> status(n_cal, 0);   // aiy_ge_options.status_out bits
   const int max_cyc = o->max_egm_cycles > 0 ? o->max_egm_cycles : 5000;
   const int max_hist = o->max_hist_iter > 0 ? o->max_hist_iter : 200000;
-  std::vector<RootSearch> rs(n_cal);
-  for (int c = 0; c < n_cal; ++c) {
-    const double lo0 = o->r_lo ? o->r_lo[c] : -0.5 * M->delta[c];
-    const double hi0 = o->r_hi ? o->r_hi[c] : 1.0 / M->disc[c] - 1.0 - 1e-9;
-    rs[c].init(lo0, hi0, o->r_tol, o->method, o->loose_bracket != 0 ? h->ge_logsec : 0);
-  }
-  std::vector<double> R(n_cal), w(n_cal), Kd(n_cal), Ks(n_cal, 0.0), Ks_fin(n_cal, 0.0);
+  // every calibration's search (ev[c].final_ks marks it for the final pass below)
+  std::vector<GeEval> ev(n_cal);
+  for (int c = 0; c < n_cal; ++c)
+    ev[c].init(eo, o->r_lo ? o->r_lo[c] : GeEval::default_lo(M->delta[c]),
+               o->r_hi ? o->r_hi[c] : GeEval::default_hi(M->disc[c]));
+  std::vector<double> R(n_cal), w(n_cal), Ks(n_cal, 0.0), Ks_fin(n_cal, 0.0);
   std::vector<int32_t> cyc(n_cal), its(n_cal);
   std::vector<double> dist(n_cal);
   aiy_egm_dims dims{n_cal, S, 1, n_a};
@@ -163,24 +159,28 @@ extern "C" int32_t aiy_ge_stationary(aiy_handle* h, const aiy_stationary_model* 
   long long cyc_sum = 0, it_sum = 0;
   // a calibration whose search ends on an evaluation at looser tolerances (loose
   // bracketing, or Brent's adaptive distribution tolerance) has that r evaluated once more at
-  // egm_tol / hist_tol (warm: a few cycles and matvecs) before its K_s is reported; fin[c] marks
-  // it for that final pass, which evaluates r_cur[c] (the others re-evaluate their rs.x as every
+  // egm_tol / hist_tol (warm: a few cycles and matvecs) before its K_s is reported; final_ks marks
+  // it for that final pass, which evaluates its r_cur (the others re-evaluate their rs.x as every
   // step does for finished calibrations)
-  std::vector<char> fin(n_cal, 0);
+  // (where this loop and the resident kernel disagree, would be fixed
+  // here: this loop goes on planning and accepting finished calibrations -- accept() moves their
+  // r_cur to rs.x and final_ks is never cleared -- and it tests max_steps before the final pass
+  // is decided; the kernel leaves a finished search alone and always runs its final pass)
   bool final_pass = false;
   while (steps < o->max_steps || final_pass) {
     bool all_done = true;
-    for (int c = 0; c < n_cal; ++c) all_done = all_done && rs[c].done;
+    for (int c = 0; c < n_cal; ++c) all_done = all_done && ev[c].rs.done;
     if (all_done && !final_pass) {
-      for (int c = 0; c < n_cal; ++c) final_pass = final_pass || fin[c];
+      for (int c = 0; c < n_cal; ++c) final_pass = final_pass || ev[c].final_ks;
       if (!final_pass) break;
     }
     for (int c = 0; c < n_cal; ++c) {
-      const double r = fin[c] ? r_cur[c] : rs[c].x, a = M->alpha[c], d = M->delta[c];
-      const double KtoL = std::pow(a / (r + d), 1.0 / (1.0 - a));
-      R[c] = 1.0 + r;
-      w[c] = (1.0 - a) * std::pow(KtoL, a);
-      Kd[c] = KtoL;
+      ev[c].plan(eo, M->alpha[c], M->delta[c]);
+      R[c] = ev[c].R;
+      w[c] = ev[c].wage;
+      etol[c] = ev[c].etol;
+      htol[c] = ev[c].htol;
+      theta[c] = ev[c].theta;
     }
     AIY_HIP(h, hipMemcpyAsync(Rc, R.data(), sizeof(double) * n_cal, hipMemcpyHostToDevice, st));
     AIY_HIP(h, hipMemcpyAsync(wc, w.data(), sizeof(double) * n_cal, hipMemcpyHostToDevice, st));
@@ -188,18 +188,6 @@ extern "C" int32_t aiy_ge_stationary(aiy_handle* h, const aiy_stationary_model* 
                        Mn);
     AIY_CHECK_LAUNCH(h);
     if (loose_on) {
-      for (int c = 0; c < n_cal; ++c) {
-        // bracketing evaluations run loose (Brent's at the full tolerances)
-        loose[c] = !rs[c].brent && !rs[c].done && !refine[c];
-        etol[c] = loose[c] ? kLooseEgm : o->egm_tol;
-        htol[c] = loose[c] ? kLooseHist : o->hist_tol;
-        // Brent's evaluations at the adaptive tolerance, refined ones at the full one
-        adapt[c] = 0;
-        if (kGeAdapt && rs[c].brent && !rs[c].done && !refine[c]) {
-          htol[c] = ge_adapt_htol(fmin_rel[c], o->hist_tol, kLooseHist);
-          adapt[c] = htol[c] > o->hist_tol;
-        }
-      }
       AIY_HIP(h, hipMemcpyAsync(d_etol, etol.data(), sizeof(double) * n_cal, hipMemcpyHostToDevice, st));
       AIY_HIP(h, hipMemcpyAsync(d_htol, htol.data(), sizeof(double) * n_cal, hipMemcpyHostToDevice, st));
       h->egm_tolv = d_etol;
@@ -210,12 +198,7 @@ extern "C" int32_t aiy_ge_stationary(aiy_handle* h, const aiy_stationary_model* 
     // secant starts (steps >= 2, warm): x0 = cur + theta (cur - prev); the current
     // evaluation's tables / mass become the previous ones (pointer swap)
     const bool secant = o->secant_start && o->warm_egm && o->warm_hist && steps >= 2;
-    if (secant) {
-      for (int c = 0; c < n_cal; ++c) {
-        const double den = r_cur[c] - r_prev[c];
-        double th = den != 0.0 && !fin[c] ? (rs[c].x - r_cur[c]) / den : 0.0;
-        theta[c] = std::isfinite(th) ? std::max(-1.0, std::min(1.0, th)) : 0.0;
-      }
+    if (secant) {   // (theta = 0, a plain copy, for the calibrations of a final pass)
       AIY_HIP(h, hipMemcpyAsync(d_th, theta.data(), sizeof(double) * n_cal, hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(secant_start_kernel, dim3(sec_blocks), dim3(256), 0, st, tab_per, n_cal, d_th, tm, pm, im);
       hipLaunchKernelGGL(secant_start_kernel, dim3(sec_blocks), dim3(256), 0, st, tab_per, n_cal, d_th, tc, pc, ic);
@@ -266,7 +249,7 @@ extern "C" int32_t aiy_ge_stationary(aiy_handle* h, const aiy_stationary_model* 
     if (rc) break;
     if (final_pass) {   // K_s of the marked calibrations at the full tolerances; the search is over
       for (int c = 0; c < n_cal; ++c)
-        if (fin[c]) {
+        if (ev[c].final_ks) {
           cyc_sum += cyc[c];
           it_sum += its[c];
           if (cyc[c] > max_cyc && !(dist[c] <= etol[c])) status[c] |= 1;
@@ -276,23 +259,13 @@ extern "C" int32_t aiy_ge_stationary(aiy_handle* h, const aiy_stationary_model* 
       break;
     }
     for (int c = 0; c < n_cal; ++c) {
-      const bool was_done = rs[c].done;
       cyc_sum += cyc[c];
       it_sum += its[c];
       // an evaluation that stopped at an iteration cap still moves the bracket by its sign;
       // the caller learns of it through status_out
-      if (!rs[c].done && cyc[c] > max_cyc && !(dist[c] <= etol[c])) status[c] |= 1;
-      if (!rs[c].done && its[c] >= max_hist) status[c] |= 2;
-      r_prev[c] = r_cur[c];
-      r_cur[c] = rs[c].x;
-      const double f = Ks[c] - Kd[c];
-      refine[c] = (loose[c] && !(std::fabs(f) >= kGeSignMargin * Kd[c])) ||   // NaN: refine
-                  (adapt[c] && !(std::fabs(f) >= kGeAdaptMargin * htol[c] * Kd[c]));
-      if (!refine[c]) {
-        rs[c].update(f, Kd[c]);
-        fmin_rel[c] = std::min(fmin_rel[c], std::fabs(f) / Kd[c]);
-      }
-      if (!was_done && rs[c].done) fin[c] = loose[c] || adapt[c];
+      if (!ev[c].rs.done && cyc[c] > max_cyc && !(dist[c] <= etol[c])) status[c] |= 1;
+      if (!ev[c].rs.done && its[c] >= max_hist) status[c] |= 2;
+      ev[c].accept(Ks[c]);
       Ks_fin[c] = Ks[c];
     }
     ++steps;
@@ -302,13 +275,12 @@ extern "C" int32_t aiy_ge_stationary(aiy_handle* h, const aiy_stationary_model* 
   h->egm_tolv = h->egm_tolh = h->hist_tolv = nullptr;
   if (rc) return rc;
   for (int c = 0; c < n_cal; ++c) {
-    const double r = rs[c].x, a = M->alpha[c], d = M->delta[c];
-    r_out[c] = r;
-    K_out[c] = std::pow(a / (r + d), 1.0 / (1.0 - a));
+    r_out[c] = ev[c].rs.x;
+    K_out[c] = ge_prices(ev[c].rs.x, M->alpha[c], M->delta[c]).Kd;
     if (Ks_out) Ks_out[c] = Ks_fin[c];
   }
   for (int c = 0; c < n_cal; ++c)
-    if (!rs[c].done) status[c] |= 4;
+    if (!ev[c].rs.done) status[c] |= 4;
   if (o->status_out)
     for (int c = 0; c < n_cal; ++c) o->status_out[c] = status[c];
   if (steps_out) *steps_out = steps;

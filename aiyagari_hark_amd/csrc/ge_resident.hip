@@ -8,8 +8,9 @@
 // clusters as the resident histogram, hist_resident.hip) that runs, with no host round
 // trip and no waiting for other calibrations:
 //
-//   loop over K_s(r) evaluations (the RootSearch of ge_search.h, every workgroup of the
-//   cluster on bit-identical inputs):
+//   loop over K_s(r) evaluations (the search policy GeEval of ge_search.h -- plan() before an
+//   evaluation, accept() after it, the same two calls as ge.hip's loop -- every workgroup of
+//   the cluster on bit-identical inputs):
 //     prices      R = 1 + r, w = (1 - alpha) (alpha / (r + delta))^(alpha / (1 - alpha))
 //     start       secant start of the household tables and the mass from the last two
 //                 evaluations (x0 = cur + theta (cur - prev)), as ge.hip
@@ -25,6 +26,11 @@
 //     histogram   BiCGSTAB on (I - T) mass = 0 (hist_bicg.h, the kernel of hist_krylov.hip)
 //     K_s         sum mass a (cluster reduction); f = K_s - K_d; loose-bracketing sign test
 //   until the search is done; workgroup 0 writes r, K, K_s, the counts and the status.
+//
+// The kernel is one body (one register allocation): its phases -- ge_vote, ge_secant_tables,
+// ge_household_solve (ge_egm_dispatch, ge_extrapolate, ge_anderson), the lottery, ge_mass_start,
+// the BiCGSTAB call, ge_capital, ge_write_out -- are __forceinline__ functions over GeCtx and
+// the file-scope LDS.
 //
 // The launch ends when the slowest calibration's whole search ends (the host loop's launches
 // each waited for the slowest calibration of that step).  Workgroup placement: block b runs
@@ -145,16 +151,15 @@ constexpr int kGeProf = 8;
 constexpr int kGeEvLog = 32;
 constexpr int kGeEvRec = 6;
 
-// Search state of one calibration, one copy per workgroup (thread 0 writes, all read).
+// Search state of one calibration, one copy per workgroup (thread 0 writes, all read): the
+// search and the planned evaluation (GeEval, ge_search.h), and the device's own bookkeeping.
 struct GeState {
-  RootSearch rs;
-  double R, wage, Kd, etol, htol, theta, r_cur, r_prev, Ks, dist, lam_prev, fext;
-  double fmin;             // smallest |K_s - K_d| / K_d accepted so far (adaptive tolerance)
-  int adapt;               // this evaluation runs at an adaptive histogram tolerance
-  int steps, loose, refine, warm_egm, secant, fresh_mass, status, n, stop, nan_stop, moved, extrap;
+  GeEval ev;
+  GeEvalOpts opt;          // the launch's search options: thread 0 plans from LDS (planning from the
+                           // kernel arguments cost 32-48 B of scratch per lane)
+  double Ks, dist, lam_prev, fext;
+  int status, n, stop, nan_stop, moved, extrap;
   int in_hist;             // stopped (rebalancing) inside this evaluation's distribution solve
-  int final_ks;            // the search ended on a loose or adaptive-tolerance evaluation: that r is
-                           // evaluated once more at the full tolerances before K_s is reported
   int buf[kGeBufs];        // roles: 0 ping, 1 pong, 2 cur, 3 prev, 4 init -> buffer index
   long long cyc_sum, its_sum;
   unsigned long long t_egm, t_lot, t_hist, t_k, t0, t_ev0;
@@ -341,8 +346,8 @@ __device__ __forceinline__ double ge_egm_cycle(int S, int n_a, int j0, int j1, c
   return dmax;
 }
 
-// The kernel's LDS at file scope, so the search loop, the EGM cycle and the lottery (their
-// own non-inlined functions, each with its own register allocation) address it directly.
+// The kernel's LDS at file scope, so the phases of the search (__forceinline__ functions: the
+// kernel is one body with one register allocation) address it directly.
 constexpr int kGeSmax = 8;    // the largest resident state count (Table II: 7)
 extern __shared__ double ge_dyn[];                 // histogram: span buffer + v; EGM: V tiles + windows
 __shared__ double ge_s_part[kHcRed][kGeWavesMax];
@@ -400,99 +405,395 @@ __device__ __forceinline__ void ge_lottery_fn(int S, int n_a, int j0, int j1, co
                      [](int, int) {}, [](int, int, double) {});
 }
 
+// What the phases of one workgroup's search share: its calibration's arrays, its own asset
+// columns [j0, j1) and its place (workgroup w of G, launch-local cluster lc); built once at
+// kernel entry.  (The counts nb / ne of the plain barriers / cluster reductions passed travel
+// beside it: hk_solve_* takes their addresses, which would pin the whole struct in memory.)
+struct GeCtx {
+  double* tab;            // the calibration's kGeBufs table buffers
+  double* X;              // mass
+  double* PX;             // previous evaluation's mass
+  int* LO;
+  double* WL;
+  unsigned* ctr;
+  unsigned long long* cw;     // counting-barrier words
+  unsigned long long* gran;
+  const double* a_grid;
+  double beta, gam;
+  size_t tab_sz;
+  int j0, j1, w, G, S, n_a, cal, lc;
+  __device__ __forceinline__ double* tabm(int b) const { return tab + (size_t)b * 2 * tab_sz; }
+  __device__ __forceinline__ double* tabc(int b) const { return tab + (size_t)b * 2 * tab_sz + tab_sz; }
+};
+
+__device__ __forceinline__ GeEvalOpts ge_eval_opts(const GeRun& g) {
+  return {g.method, g.loose, g.logsec, g.warm_egm, g.warm_hist, g.secant, g.r_tol, g.egm_tol, g.hist_tol, g.loose_hist};
+}
+
+// plain cluster barrier after the workgroup's stores drained; false: timed out (the kernel returns)
+__device__ __forceinline__ bool ge_barrier(const GeCtx& cx, unsigned& nb, unsigned* err) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ++nb;
+  return hc_barrier(err, cx.ctr, (unsigned)cx.G * nb, &ge_s_flag);
+}
+
+// A vote of the cluster on its counting barrier: every workgroup's thread 0 adds `flag` (bit
+// fields, each counted over the cluster) to the parity word of this barrier; dlt (thread 0) is
+// what the cluster added.  Every workgroup sees the same dlt, so all take the same decision.
+__device__ __forceinline__ bool ge_vote(const GeCtx& cx, unsigned* err, unsigned flag, unsigned& dlt) {
+  GeState& st = ge_st;
+  const int tid = threadIdx.x;
+  if (tid == 0) ++st.nbc;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const unsigned k = st.nbc, par = k & 1u;
+  if (!hc_barrier_count(err, &cx.cw[par], (unsigned)cx.G * ((k + par) / 2), flag, &ge_s_nc, &ge_s_flag))
+    return false;
+  if (tid == 0) {
+    dlt = ge_s_nc - st.nc_prev[par];
+    st.nc_prev[par] = ge_s_nc;
+  }
+  return true;
+}
+
+// Secant start of the household tables into `init` (own nodes): cur + theta (cur - prev).
+template <int TH>
+__device__ __forceinline__ void ge_secant_tables(const GeCtx& cx, int b_cur, int b_prev, int b_init, double theta) {
+  const int tid = threadIdx.x, n1 = cx.n_a + 1;
+  for (int s = 0; s < cx.S; ++s) {
+    for (int k = cx.j0 + tid; k < cx.j1; k += TH) {
+      const size_t o = (size_t)s * n1 + k + 1;
+      const double cm = load_f64_agent(&cx.tabm(b_cur)[o]), pm = load_f64_agent(&cx.tabm(b_prev)[o]);
+      const double cc = load_f64_agent(&cx.tabc(b_cur)[o]), pc = load_f64_agent(&cx.tabc(b_prev)[o]);
+      store_f64_agent(&cx.tabm(b_init)[o], theta == 0.0 ? cm : cm + theta * (cm - pm));
+      store_f64_agent(&cx.tabc(b_init)[o], theta == 0.0 ? cc : cc + theta * (cc - pc));
+    }
+    if (cx.j0 == 0 && tid == 0) {
+      store_f64_agent(&cx.tabm(b_init)[(size_t)s * n1], kBorrowNode);
+      store_f64_agent(&cx.tabc(b_init)[(size_t)s * n1], kBorrowNode);
+    }
+  }
+}
+
+// one EGM cycle with the marginal utility of the calibration's CRRA (pk: 1, 3, 5, else general)
+template <int SMAX, int SC, int NW>
+__device__ __forceinline__ double ge_egm_dispatch(const GeCtx& cx, int pk, const double* sm, const double* sc, double* dm,
+                                                  double* dc, bool track, double R, double* ring) {
+  if (pk == 1)
+    return ge_egm_cycle_fn<SMAX, SC, 1, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, dm, dc, track, R, cx.beta,
+                                            cx.gam, ring);
+  if (pk == 3)
+    return ge_egm_cycle_fn<SMAX, SC, 3, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, dm, dc, track, R, cx.beta,
+                                            cx.gam, ring);
+  if (pk == 5)
+    return ge_egm_cycle_fn<SMAX, SC, 5, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, dm, dc, track, R, cx.beta,
+                                            cx.gam, ring);
+  return ge_egm_cycle_fn<SMAX, SC, 0, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, dm, dc, track, R, cx.beta,
+                                          cx.gam, ring);
+}
+
+// Geometric extrapolation at a check (ge_search.h egm_extrap_factor; egm.hip egm_extrap_kernel):
+// the tables of cycle n (b_dst) move along their change from cycle n - 1 (b_src), own nodes.
+template <int TH>
+__device__ __forceinline__ bool ge_extrapolate(const GeCtx& cx, unsigned& nb, unsigned* err, int b_dst, int b_src,
+                                               double dclu, int n) {
+  GeState& st = ge_st;
+  const int tid = threadIdx.x, n1 = cx.n_a + 1;
+  if (tid == 0) {
+    st.fext = egm_extrap_factor(dclu, st.dist, st.ev.etol, n, st.lam_prev);
+    if (st.fext != 0.0) st.moved = 1;
+  }
+  __syncthreads();
+  const double f = st.fext;
+  if (f != 0.0) {
+    double* cm = cx.tabm(b_dst);
+    double* cc = cx.tabc(b_dst);
+    const double* pm = cx.tabm(b_src);
+    const double* pc = cx.tabc(b_src);
+    for (int s = 0; s < cx.S; ++s)
+      for (int k = cx.j0 + tid; k < cx.j1; k += TH) {
+        const size_t o = (size_t)s * n1 + k + 1;
+        const double x = load_f64_agent(&cm[o]), y = load_f64_agent(&cc[o]);
+        store_f64_agent(&cm[o], x + f * (x - load_f64_agent(&pm[o])));
+        store_f64_agent(&cc[o], y + f * (y - load_f64_agent(&pc[o])));
+      }
+    if (!ge_barrier(cx, nb, err)) return false;
+  }
+  return true;
+}
+
+// slot of cycle c's c table in the Anderson ring
+__device__ __forceinline__ double* ge_ring(const GeCtx& cx, const GeRun& g, int c) {
+  return g.aah + ((size_t)cx.cal * kGeAaHist + (size_t)(c % kGeAaHist)) * cx.S * cx.n_a;
+}
+
+// Type-II Anderson mix (ge_search.h aa_*) over the plain chain w0 .. w4 = the outputs of cycles
+// n - 4 .. n (p >= kGeAaHist: no mix inside the window).  The Gram terms go through two cluster
+// reductions in fixed order, so every workgroup solves the same 3 x 3 system to the same bits;
+// x_{n+1} = w4 - dF gamma replaces the cycle's output (own nodes, m = a + c), visible to every
+// workgroup after a barrier.
+template <int TH>
+__device__ __forceinline__ bool ge_anderson(const GeCtx& cx, unsigned& nb, unsigned& ne, const GeRun& g, int n,
+                                            int b_dst) {
+  static_assert(kGeAaM == 3 && kGeAaHist == 5, "the mixing is written for m = 3");
+  const int tid = threadIdx.x, n1 = cx.n_a + 1;
+  const double* W0 = ge_ring(cx, g, n - 4);
+  const double* W1 = ge_ring(cx, g, n - 3);
+  const double* W2 = ge_ring(cx, g, n - 2);
+  const double* W3 = ge_ring(cx, g, n - 1);
+  const double* W4 = ge_ring(cx, g, n);
+  double gp[9];
+  for (int q = 0; q < 9; ++q) gp[q] = 0.0;
+  for (int s = 0; s < cx.S; ++s)
+    for (int k = cx.j0 + tid; k < cx.j1; k += TH) {
+      const size_t o = (size_t)s * cx.n_a + k;
+      const double w0 = load_f64_agent(W0 + o), w1 = load_f64_agent(W1 + o), w2 = load_f64_agent(W2 + o);
+      const double w3 = load_f64_agent(W3 + o), w4 = load_f64_agent(W4 + o);
+      aa_gram_add(w0, w1, w2, w3, w4, gp);
+    }
+  double gs[9], gam[3];
+  if (!ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, gp, 6, 0u, ge_s_part, ge_s_res, &ge_s_flag, g.err)) return false;
+  for (int q = 0; q < 6; ++q) gs[q] = ge_s_res[q];
+  if (!ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, gp + 6, 3, 0u, ge_s_part, ge_s_res, &ge_s_flag, g.err)) return false;
+  for (int q = 0; q < 3; ++q) gs[6 + q] = ge_s_res[q];
+  if (aa_solve(gs, gam)) {
+    double* dm = cx.tabm(b_dst);
+    double* dc = cx.tabc(b_dst);
+    for (int s = 0; s < cx.S; ++s)
+      for (int k = cx.j0 + tid; k < cx.j1; k += TH) {
+        const size_t o = (size_t)s * cx.n_a + k;
+        const double w1 = load_f64_agent(W1 + o), w2 = load_f64_agent(W2 + o);
+        const double w3 = load_f64_agent(W3 + o), w4 = load_f64_agent(W4 + o);
+        const double cn = aa_mix(gam, w1, w2, w3, w4);
+        store_f64_agent(&dm[(size_t)s * n1 + k + 1], cx.a_grid[k] + cn);   // AS:1499
+        store_f64_agent(&dc[(size_t)s * n1 + k + 1], cn);
+      }
+    if (tid == 0) ge_st.moved = 1;
+    if (!ge_barrier(cx, nb, g.err)) return false;
+  }
+  return true;
+}
+
+// The household solve ([HARK] solve_agent: cycles until the sup-norm change of the tables is
+// <= tol, NaN stops; cold -- init_m == nullptr -- cycle 1 from the terminal guess).  Returns
+// the buffer of the final tables, -1: a barrier timed out.
+template <int SMAX, int SC, int TH>
+__device__ __forceinline__ int ge_household_solve(const GeCtx& cx, unsigned& nb, unsigned& ne, const GeRun& g, int pk,
+                                                  double R, const double* init_m, const double* init_c) {
+  constexpr int NW = TH / kWave;
+  GeState& st = ge_st;
+  const int tid = threadIdx.x;
+  int final_buf = -1;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if (!ge_barrier(cx, nb, g.err)) return -1;   // every workgroup's start tables visible
+    // Anderson mixing (the first attempt; a NaN after a mix reruns the solve plain) replaces
+    // the geometric extrapolation
+    const bool aa = g.aa_period > 0 && attempt == 0;
+    const bool ext = st.extrap != 0 && attempt == 0 && !aa;
+    if (tid == 0) {
+      st.lam_prev = -1.0;
+      st.moved = 0;
+      st.nan_stop = 0;
+    }
+    int n = 1;
+    const int last_allowed = g.max_cyc + 1;
+    bool converged = false;
+    while (true) {
+      const int b_dst = st.buf[n & 1], b_src = st.buf[(n - 1) & 1];
+      const double* sm = n == 1 ? init_m : cx.tabm(b_src);
+      const double* sc = n == 1 ? init_c : cx.tabc(b_src);
+      const bool track = n >= 2;
+      const double dl = ge_egm_dispatch<SMAX, SC, NW>(cx, pk, sm, sc, cx.tabm(b_dst), cx.tabc(b_dst), track, R,
+                                                      aa ? ge_ring(cx, g, n) : nullptr);
+      // cluster distance: the value itself at the extrapolation checks (cycles 32k - 1,
+      // 32k), else only its two facts (some part > tol; some part NaN) on a counting barrier
+      const int xp = g.extrap_period;
+      const bool want_value = ext && n >= xp - 1 && ((n % xp) == xp - 1 || (n % xp) == 0);
+      double dclu = 0.0;
+      bool go;
+      if (want_value) {
+        double v[1] = {dl};
+        if (!ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, v, 1, 1u, ge_s_part, ge_s_res, &ge_s_flag, g.err)) return -1;
+        dclu = ge_s_res[0];
+        go = dclu > st.ev.etol;   // NaN: stop (HARK: go = distance > tolerance)
+        if (tid == 0) st.nan_stop = dclu != dclu;
+      } else {
+        const double dw = wave_nan_max(dl);
+        if ((tid & (kWave - 1)) == 0) ge_s_part[0][tid / kWave] = dw;
+        __syncthreads();
+        unsigned flag = 0u, dlt = 0u;
+        if (tid == 0) {
+          double d = ge_s_part[0][0];
+          for (int q = 1; q < TH / kWave; ++q) d = nan_max(d, ge_s_part[0][q]);
+          flag = (d > st.ev.etol ? 1u : 0u) | (d != d ? (1u << 16) : 0u);
+        }
+        if (!ge_vote(cx, g.err, flag, dlt)) return -1;
+        if (tid == 0) {
+          st.stop = (dlt & 0xffffu) == 0u || (dlt >> 16) != 0u;
+          st.nan_stop = (dlt >> 16) != 0u;
+        }
+        __syncthreads();
+        go = !st.stop;
+      }
+      if (track && !go) {
+        converged = true;
+        break;
+      }
+      if (n >= last_allowed) break;
+      if (want_value && (n % xp) == 0) {
+        if (!ge_extrapolate<TH>(cx, nb, g.err, b_dst, b_src, dclu, n)) return -1;
+      } else if (want_value) {
+        if (tid == 0) st.dist = dclu;
+      }
+      if (aa && n >= g.aa_period && n >= kGeAaHist + 1 && (n % g.aa_period) == 0) {
+        if (!ge_anderson<TH>(cx, nb, ne, g, n, b_dst)) return -1;
+      }
+      ++n;
+    }
+    if (tid == 0) {
+      st.n = n;
+      if (!converged) st.status |= 1;
+    }
+    __syncthreads();
+    final_buf = st.buf[n & 1];
+    // an extrapolated solve that ended in NaN: the whole solve again, plain (ge.hip)
+    if (!(st.moved && st.nan_stop)) break;
+    if (tid == 0) {
+      st.extrap = 0;
+      st.status &= ~1;
+    }
+    __syncthreads();
+  }
+  return final_buf;
+}
+
+// The distribution's start (own columns): uniform, or the last mass -- with a secant start its
+// secant extrapolation from the last two -- the last one kept as the previous mass.
+template <int TH>
+__device__ __forceinline__ void ge_mass_start(const GeCtx& cx, bool fresh, bool warm, bool secant, double theta) {
+  const int tid = threadIdx.x;
+  if (fresh) {
+    const double u0 = 1.0 / ((double)cx.S * cx.n_a);
+    for (int s = 0; s < cx.S; ++s)
+      for (int k = cx.j0 + tid; k < cx.j1; k += TH) cx.X[(size_t)s * cx.n_a + k] = u0;
+  } else if (warm) {
+    for (int s = 0; s < cx.S; ++s)
+      for (int k = cx.j0 + tid; k < cx.j1; k += TH) {
+        const size_t o = (size_t)s * cx.n_a + k;
+        const double x = cx.X[o];
+        if (secant) cx.X[o] = theta == 0.0 ? x : x + theta * (x - cx.PX[o]);
+        cx.PX[o] = x;
+      }
+  }
+}
+
+// K_s = sum mass a over the cluster, into ge_s_res[0] of every workgroup
+template <int TH>
+__device__ __forceinline__ bool ge_capital(const GeCtx& cx, unsigned& ne, unsigned* err) {
+  double part = 0.0;
+  for (int k = cx.j0 + (int)threadIdx.x; k < cx.j1; k += TH) {
+    double ms = 0.0;
+    for (int s = 0; s < cx.S; ++s) ms += cx.X[(size_t)s * cx.n_a + k];
+    part += ms * cx.a_grid[k];
+  }
+  double v[1] = {part};
+  return ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, v, 1, 0u, ge_s_part, ge_s_res, &ge_s_flag, err);
+}
+
+// a finished search's outputs and profile (workgroup 0, thread 0)
+__device__ __forceinline__ void ge_write_out(const GeCtx& cx, const GeRun& g, const GeCalDev& cd) {
+  const GeState& st = ge_st;
+  const int cal = cx.cal;
+  __hip_atomic_fetch_add(to_global(g.done_ctr), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  g.out_done[cal] = 1;
+  g.out_r[cal] = st.ev.rs.x;
+  g.out_K[cal] = ge_prices(st.ev.rs.x, cd.alpha, cd.delta).Kd;
+  g.out_Ks[cal] = st.Ks;
+  g.out_steps[cal] = st.ev.steps;
+  g.out_cyc[cal] = (int)min(st.cyc_sum, 0x7fffffffll);
+  g.out_its[cal] = (int)min(st.its_sum, 0x7fffffffll);
+  g.out_status[cal] = st.status | (st.ev.rs.done ? 0 : 4);
+  double* pf = g.out_prof + (size_t)cal * kGeProf;
+  pf[0] = st.t_egm * 0.01;
+  pf[1] = st.t_lot * 0.01;
+  pf[2] = st.t_hist * 0.01;
+  pf[3] = st.t_k * 0.01;
+  pf[4] = (__builtin_amdgcn_s_memrealtime() - st.t0) * 0.01;
+  pf[5] = (double)st.cyc_sum;
+  pf[6] = (double)st.its_sum;
+  pf[7] = (double)st.ev.steps;
+}
+
+// setup -> while the search is not over { stop vote; plan; household solve; lottery; mass
+// start; distribution solve; K_s; accept } -> save the stopped search, or write it out
 template <int SMAX, int SC, int KC, int TH>
 __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
   constexpr int NW = TH / kWave;
   static_assert(SMAX <= kGeSmax, "file-scope LDS sized for kGeSmax states");
   GeState& st = ge_st;
-  double (*s_part)[kGeWavesMax] = ge_s_part;
-  double* s_res = ge_s_res;
-  int& s_flag = ge_s_flag;
-  double* s_Pe = ge_s_Pe;
-  double* s_Wl = ge_s_Wl;
-  int* s_hint = ge_s_hint;
-  unsigned& s_nc = ge_s_nc;
 
   const int per = gridDim.x >> 3;
   const int u = (blockIdx.x & 7) * per + (blockIdx.x >> 3);   // XCD-contiguous work order
   if (u >= g.n_work) return;
-  const int G = g.G, S = g.S, n_a = g.n_a, n1 = n_a + 1;
-  const int lc = u / G, w = u - lc * G;   // launch-local cluster, workgroup in it
-  const int cal = g.cal_ids[lc];
+  const int G = g.G, S = g.S, n_a = g.n_a;
   const int tid = threadIdx.x;
-  const int j0 = w * g.nj, j1 = min(j0 + g.nj, n_a);
-  const double* a_grid = g.a_grid + (size_t)cal * n_a;
-  const double beta = g.beta[cal], gam = g.crra[cal];
+  GeCtx cx;
+  cx.G = G; cx.S = S; cx.n_a = n_a;
+  cx.lc = u / G; cx.w = u - cx.lc * G;   // launch-local cluster, workgroup in it
+  const int lc = cx.lc, w = cx.w, cal = g.cal_ids[lc];
+  cx.cal = cal;
+  cx.j0 = w * g.nj; cx.j1 = min(cx.j0 + g.nj, n_a);
+  const int j0 = cx.j0, j1 = cx.j1;
+  cx.a_grid = g.a_grid + (size_t)cal * n_a;
+  cx.beta = g.beta[cal]; cx.gam = g.crra[cal];
   const GeCalDev cd = g.cal[cal];
-  const size_t tab_sz = (size_t)S * n1;
-  double* tab = g.tab + (size_t)cal * kGeBufs * 2 * tab_sz;
-  auto tabm = [&](int b) { return tab + (size_t)b * 2 * tab_sz; };
-  auto tabc = [&](int b) { return tab + (size_t)b * 2 * tab_sz + tab_sz; };
+  cx.tab_sz = (size_t)S * (n_a + 1);
+  cx.tab = g.tab + (size_t)cal * kGeBufs * 2 * cx.tab_sz;
   const size_t row0 = (size_t)cal * S * n_a;
-  double* X = g.mass + row0;
-  double* PX = g.pmass + row0;
-  int* LO = g.lo + row0;
-  double* WL = g.wlo + row0;
-  unsigned* ctr = g.ctr + (size_t)lc * kHcCtrStride;
-  unsigned long long* cw = reinterpret_cast<unsigned long long*>(ctr + 2);   // counting-barrier words
-  unsigned long long* gran = g.gran + (size_t)lc * 2 * G * kHcRedRec;
+  cx.X = g.mass + row0;
+  cx.PX = g.pmass + row0;
+  cx.LO = g.lo + row0;
+  cx.WL = g.wlo + row0;
+  cx.ctr = g.ctr + (size_t)lc * kHcCtrStride;
+  cx.cw = reinterpret_cast<unsigned long long*>(cx.ctr + 2);
+  cx.gran = g.gran + (size_t)lc * 2 * G * kHcRedRec;
   unsigned nb = 0, ne = 0;   // plain barriers / reductions passed (hk_solve counts on)
-  const int pk = gam == 1.0 ? 1 : (gam == 3.0 ? 3 : (gam == 5.0 ? 5 : 0));
+  const int pk = cx.gam == 1.0 ? 1 : (cx.gam == 3.0 ? 3 : (cx.gam == 5.0 ? 5 : 0));
 
-
-  for (int q = tid; q < S * S; q += TH) s_Pe[q] = g.P[(size_t)cal * S * S + q];
-  for (int q = tid; q < kGeMaxTiles * SMAX; q += TH) s_hint[q] = -1;
+  for (int q = tid; q < S * S; q += TH) ge_s_Pe[q] = g.P[(size_t)cal * S * S + q];
+  for (int q = tid; q < kGeMaxTiles * SMAX; q += TH) ge_s_hint[q] = -1;
   if (tid == 0) {
     if (g.resume[cal]) {   // a calibration stopped by an earlier launch: its search goes on
       st = g.saved[cal];
       st.t0 = __builtin_amdgcn_s_memrealtime() - st.t0;   // saved: the time spent so far
     } else {
-      st.rs.init(cd.r_lo, cd.r_hi, g.r_tol, g.method, g.loose ? g.logsec : 0);
-      st.r_cur = st.r_prev = 0.0;
+      st.ev.init(ge_eval_opts(g), cd.r_lo, cd.r_hi);
       st.Ks = 0.0;
-      st.fmin = __builtin_inf();
-      st.adapt = 0;
-      st.steps = 0;
-      st.refine = 0;
       st.in_hist = 0;
-      st.final_ks = 0;
       st.status = 0;
       st.cyc_sum = st.its_sum = 0;
       for (int b = 0; b < kGeBufs; ++b) st.buf[b] = b;
       st.t_egm = st.t_lot = st.t_hist = st.t_k = 0ull;
       st.t0 = __builtin_amdgcn_s_memrealtime();
     }
+    st.opt = ge_eval_opts(g);
     st.nc_prev[0] = st.nc_prev[1] = 0u;   // this launch's counting-barrier words start at 0
     st.nbc = 0u;
   }
   __syncthreads();
-  auto plain_barrier = [&]() -> bool {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ++nb;
-    return hc_barrier(g.err, ctr, (unsigned)G * nb, &s_flag);
-  };
 
   bool stopped = false;
-  while ((!st.rs.done && st.steps < g.max_steps) || st.final_ks) {
+  while ((!st.ev.rs.done && st.ev.steps < g.max_steps) || st.ev.final_ks) {
     // ---- rebalancing stop: once stop_at calibrations of the launch have finished, the
     //      cluster leaves at this evaluation boundary (the decision: any workgroup saw it,
     //      counted on the cluster's barrier, so every workgroup takes it) ----
-    if (g.stop_at > 0 && st.steps > 0 && !st.in_hist) {
-      unsigned flag = 0u;
-      if (tid == 0) {
+    if (g.stop_at > 0 && st.ev.steps > 0 && !st.in_hist) {
+      unsigned flag = 0u, dlt = 0u;
+      if (tid == 0)
         flag = __hip_atomic_load(to_global(g.done_ctr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >=
                        (unsigned)g.stop_at ? 1u : 0u;
-        ++st.nbc;
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      const unsigned k = st.nbc, par = k & 1u;
-      if (!hc_barrier_count(g.err, &cw[par], (unsigned)G * ((k + par) / 2), flag, &s_nc, &s_flag)) return;
-      if (tid == 0) {
-        const unsigned dlt = s_nc - st.nc_prev[par];
-        st.nc_prev[par] = s_nc;
-        st.stop = dlt != 0u;
-      }
+      if (!ge_vote(cx, g.err, flag, dlt)) return;
+      if (tid == 0) st.stop = dlt != 0u;
       __syncthreads();
       if (st.stop) {
         stopped = true;
@@ -506,240 +807,23 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
     if (!st.in_hist) {
       // ---- this evaluation's prices, tolerances and starts (thread 0; identical everywhere) ----
       if (tid == 0) {
-        // (the final pass re-evaluates the LAST evaluated r at the full tolerances)
-        const double r = st.final_ks ? st.r_cur : st.rs.x, a = cd.alpha, d = cd.delta;
-        const double KtoL = pow(a / (r + d), 1.0 / (1.0 - a));
-        st.R = 1.0 + r;
-        st.wage = (1.0 - a) * pow(KtoL, a);
-        st.Kd = KtoL;
-        st.loose = g.loose && g.method == 1 && !st.rs.brent && !st.rs.done && !st.refine;
-        st.etol = st.loose ? fmax(g.egm_tol, AIY_GE_LOOSE_EGM) : g.egm_tol;
-        st.htol = st.loose ? fmax(g.hist_tol, g.loose_hist) : g.hist_tol;
-        // Brent's evaluations: the adaptive tolerance (ge_search.h), refined ones at the full one
-        st.adapt = 0;
-        if (kGeAdapt && g.loose && g.method == 1 && st.rs.brent && !st.rs.done && !st.refine) {
-          st.htol = ge_adapt_htol(st.fmin, g.hist_tol, fmax(g.hist_tol, g.loose_hist));
-          st.adapt = st.htol > g.hist_tol;
-        }
-        st.warm_egm = g.warm_egm && st.steps > 0;
-        st.secant = g.secant && g.warm_egm && g.warm_hist && st.steps >= 2 && !st.final_ks;
-        st.fresh_mass = !(g.warm_hist && st.steps > 0);
-        double th = 0.0;
-        if (st.secant) {
-          const double den = st.r_cur - st.r_prev;
-          th = den != 0.0 ? (r - st.r_cur) / den : 0.0;
-          th = isfinite(th) ? fmax(-1.0, fmin(1.0, th)) : 0.0;
-        }
-        st.theta = th;
+        st.ev.plan(st.opt, cd.alpha, cd.delta);
         st.extrap = g.extrap;
         st.moved = 0;
       }
       __syncthreads();
-      if (tid < S) s_Wl[tid] = st.wage * g.lab[(size_t)cal * S + tid];   // W l(s') (mNextArray, AS:1024)
-      const double R = st.R, theta = st.theta;
+      if (tid < S) ge_s_Wl[tid] = st.ev.wage * g.lab[(size_t)cal * S + tid];   // W l(s') (mNextArray, AS:1024)
+      const double R = st.ev.R, theta = st.ev.theta;
       // ---- starting tables: the secant start into `init` (own nodes), else cur ----
-      const bool secant = st.secant != 0, warm = st.warm_egm != 0;
+      const bool secant = st.ev.secant != 0, warm = st.ev.warm_egm != 0;
       const int b_cur = st.buf[2], b_prev = st.buf[3], b_init = st.buf[4];
-      if (secant) {
-        for (int s = 0; s < S; ++s) {
-          for (int k = j0 + tid; k < j1; k += TH) {
-            const size_t o = (size_t)s * n1 + k + 1;
-            const double cm = load_f64_agent(&tabm(b_cur)[o]), pm = load_f64_agent(&tabm(b_prev)[o]);
-            const double cc = load_f64_agent(&tabc(b_cur)[o]), pc = load_f64_agent(&tabc(b_prev)[o]);
-            store_f64_agent(&tabm(b_init)[o], theta == 0.0 ? cm : cm + theta * (cm - pm));
-            store_f64_agent(&tabc(b_init)[o], theta == 0.0 ? cc : cc + theta * (cc - pc));
-          }
-          if (j0 == 0 && tid == 0) {
-            store_f64_agent(&tabm(b_init)[(size_t)s * n1], kBorrowNode);
-            store_f64_agent(&tabc(b_init)[(size_t)s * n1], kBorrowNode);
-          }
-        }
-      }
-      // ---- the household solve ([HARK] solve_agent: cycles until the sup-norm change of the
-      //      tables is <= tol, NaN stops; cold: cycle 1 from the terminal guess) ----
+      if (secant) ge_secant_tables<TH>(cx, b_cur, b_prev, b_init, theta);
+      // ---- the household solve ----
       tp = __builtin_amdgcn_s_memrealtime();
-      const double* init_m = secant ? tabm(b_init) : (warm ? tabm(b_cur) : nullptr);
-      const double* init_c = secant ? tabc(b_init) : (warm ? tabc(b_cur) : nullptr);
-      int final_buf = -1;
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        if (!plain_barrier()) return;   // every workgroup's start tables visible
-        // Anderson mixing (the first attempt; a NaN after a mix reruns the solve plain) replaces
-        // the geometric extrapolation
-        const bool aa = g.aa_period > 0 && attempt == 0;
-        const bool ext = st.extrap != 0 && attempt == 0 && !aa;
-        auto ring_at = [&](int c) -> double* {
-          return aa ? g.aah + ((size_t)cal * kGeAaHist + (size_t)(c % kGeAaHist)) * S * n_a : nullptr;
-        };
-        if (tid == 0) {
-          st.lam_prev = -1.0;
-          st.moved = 0;
-          st.nan_stop = 0;
-        }
-        int n = 1;
-        const int last_allowed = g.max_cyc + 1;
-        bool converged = false;
-        while (true) {
-          const int b_dst = st.buf[n & 1], b_src = st.buf[(n - 1) & 1];
-          const double* sm = n == 1 ? init_m : tabm(b_src);
-          const double* sc = n == 1 ? init_c : tabc(b_src);
-          const bool track = n >= 2;
-          double dl;
-          if (pk == 1)
-            dl = ge_egm_cycle_fn<SMAX, SC, 1, NW>(S, n_a, j0, j1, a_grid, sm, sc, tabm(b_dst), tabc(b_dst), track, R, beta,
-                                              gam, ring_at(n));
-          else if (pk == 3)
-            dl = ge_egm_cycle_fn<SMAX, SC, 3, NW>(S, n_a, j0, j1, a_grid, sm, sc, tabm(b_dst), tabc(b_dst), track, R, beta,
-                                              gam, ring_at(n));
-          else if (pk == 5)
-            dl = ge_egm_cycle_fn<SMAX, SC, 5, NW>(S, n_a, j0, j1, a_grid, sm, sc, tabm(b_dst), tabc(b_dst), track, R, beta,
-                                              gam, ring_at(n));
-          else
-            dl = ge_egm_cycle_fn<SMAX, SC, 0, NW>(S, n_a, j0, j1, a_grid, sm, sc, tabm(b_dst), tabc(b_dst), track, R, beta,
-                                              gam, ring_at(n));
-          // cluster distance: the value itself at the extrapolation checks (cycles 32k - 1,
-          // 32k), else only its two facts (some part > tol; some part NaN) on a counting barrier
-          const int xp = g.extrap_period;
-          const bool want_value = ext && n >= xp - 1 && ((n % xp) == xp - 1 || (n % xp) == 0);
-          double dclu = 0.0;
-          bool go;
-          if (want_value) {
-            double v[1] = {dl};
-            if (!ge_reduce<TH>(gran, G, w, ne, v, 1, 1u, s_part, s_res, &s_flag, g.err)) return;
-            dclu = s_res[0];
-            go = dclu > st.etol;   // NaN: stop (HARK: go = distance > tolerance)
-            if (tid == 0) st.nan_stop = dclu != dclu;
-          } else {
-            const double dw = wave_nan_max(dl);
-            if ((tid & (kWave - 1)) == 0) s_part[0][tid / kWave] = dw;
-            __syncthreads();
-            unsigned flag = 0u;
-            if (tid == 0) {
-              double d = s_part[0][0];
-              for (int q = 1; q < TH / kWave; ++q) d = nan_max(d, s_part[0][q]);
-              flag = (d > st.etol ? 1u : 0u) | (d != d ? (1u << 16) : 0u);
-              ++st.nbc;
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            const unsigned k = st.nbc, par = k & 1u;
-            if (!hc_barrier_count(g.err, &cw[par], (unsigned)G * ((k + par) / 2), flag, &s_nc, &s_flag)) return;
-            if (tid == 0) {
-              const unsigned dlt = s_nc - st.nc_prev[par];
-              st.nc_prev[par] = s_nc;
-              st.stop = (dlt & 0xffffu) == 0u || (dlt >> 16) != 0u;
-              st.nan_stop = (dlt >> 16) != 0u;
-            }
-            __syncthreads();
-            go = !st.stop;
-          }
-          if (track && !go) {
-            converged = true;
-            break;
-          }
-          if (n >= last_allowed) break;
-          // geometric extrapolation at the checks (ge.hip / egm.hip egm_extrap_kernel)
-          if (want_value && (n % xp) == 0) {
-            if (tid == 0) {
-              const double d1 = dclu, d0 = st.dist, lam = d1 / d0;
-              st.fext = 0.0;
-              if (n >= 4 && d1 > 100.0 * st.etol && lam > 0.5 && lam < 0.999 && st.lam_prev > 0.0 &&
-                  fabs(lam - st.lam_prev) < 0.2 * (1.0 - lam)) {
-                st.fext = lam / (1.0 - lam);
-                st.moved = 1;
-              }
-              st.lam_prev = lam;
-            }
-            __syncthreads();
-            const double f = st.fext;
-            if (f != 0.0) {
-              double* cm = tabm(b_dst);
-              double* cc = tabc(b_dst);
-              const double* pm = tabm(b_src);
-              const double* pc = tabc(b_src);
-              for (int s = 0; s < S; ++s)
-                for (int k = j0 + tid; k < j1; k += TH) {
-                  const size_t o = (size_t)s * n1 + k + 1;
-                  const double x = load_f64_agent(&cm[o]), y = load_f64_agent(&cc[o]);
-                  store_f64_agent(&cm[o], x + f * (x - load_f64_agent(&pm[o])));
-                  store_f64_agent(&cc[o], y + f * (y - load_f64_agent(&pc[o])));
-                }
-              if (!plain_barrier()) return;
-            }
-          } else if (want_value) {
-            if (tid == 0) st.dist = dclu;
-          }
-          if (aa && n >= g.aa_period && n >= kGeAaHist + 1 && (n % g.aa_period) == 0) {
-            // type-II Anderson over the plain chain w0 .. w4 = the outputs of cycles n - 4 .. n
-            // (p >= kGeAaHist: no mix inside the window): g_i = w_{i+1} - w_i, dG_i = g_{i+1} - g_i,
-            // dF_i = w_{i+2} - w_{i+1}; gamma = argmin |g_3 - dG gamma| (Gram + 1e-12 trace
-            // regularisation, two cluster reductions in fixed order: every workgroup solves the
-            // same 3 x 3 system to the same bits); x_{n+1} = w4 - dF gamma replaces the cycle's
-            // output (own nodes, m = a + c), visible to every workgroup after a barrier
-            static_assert(kGeAaM == 3 && kGeAaHist == 5, "the mixing below is written for m = 3");
-            const double* W0 = ring_at(n - 4);
-            const double* W1 = ring_at(n - 3);
-            const double* W2 = ring_at(n - 2);
-            const double* W3 = ring_at(n - 1);
-            const double* W4 = ring_at(n);
-            double gp[9];
-            for (int q = 0; q < 9; ++q) gp[q] = 0.0;
-            for (int s = 0; s < S; ++s)
-              for (int k = j0 + tid; k < j1; k += TH) {
-                const size_t o = (size_t)s * n_a + k;
-                const double w0 = load_f64_agent(W0 + o), w1 = load_f64_agent(W1 + o), w2 = load_f64_agent(W2 + o);
-                const double w3 = load_f64_agent(W3 + o), w4 = load_f64_agent(W4 + o);
-                const double g0 = w1 - w0, g1 = w2 - w1, g2 = w3 - w2, g3 = w4 - w3;
-                const double d0 = g1 - g0, d1 = g2 - g1, d2 = g3 - g2;
-                gp[0] += d0 * d0; gp[1] += d0 * d1; gp[2] += d0 * d2;
-                gp[3] += d1 * d1; gp[4] += d1 * d2; gp[5] += d2 * d2;
-                gp[6] += d0 * g3; gp[7] += d1 * g3; gp[8] += d2 * g3;
-              }
-            if (!ge_reduce<TH>(gran, G, w, ne, gp, 6, 0u, s_part, s_res, &s_flag, g.err)) return;
-            double a00 = s_res[0], a01 = s_res[1], a02 = s_res[2], a11 = s_res[3], a12 = s_res[4], a22 = s_res[5];
-            if (!ge_reduce<TH>(gran, G, w, ne, gp + 6, 3, 0u, s_part, s_res, &s_flag, g.err)) return;
-            const double b0 = s_res[0], b1 = s_res[1], b2 = s_res[2];
-            // Cholesky of the regularised Gram matrix (symmetric positive definite)
-            const double reg = 1e-12 * (a00 + a11 + a22);
-            a00 += reg; a11 += reg; a22 += reg;
-            const double l00 = sqrt(a00), l10 = a01 / l00, l20 = a02 / l00;
-            const double l11 = sqrt(a11 - l10 * l10), l21 = (a12 - l20 * l10) / l11;
-            const double l22 = sqrt(a22 - l20 * l20 - l21 * l21);
-            const double y0 = b0 / l00, y1 = (b1 - l10 * y0) / l11, y2 = (b2 - l20 * y0 - l21 * y1) / l22;
-            const double c2 = y2 / l22, c1 = (y1 - l21 * c2) / l11, c0 = (y0 - l10 * c1 - l20 * c2) / l00;
-            // (a degenerate or non-finite system -- a converging chain whose differences vanish,
-            // NaN nodes -- skips the mix: the cycle's output stands)
-            if (isfinite(c0) && isfinite(c1) && isfinite(c2) && reg > 0.0) {
-              double* dm = tabm(b_dst);
-              double* dc = tabc(b_dst);
-              for (int s = 0; s < S; ++s)
-                for (int k = j0 + tid; k < j1; k += TH) {
-                  const size_t o = (size_t)s * n_a + k;
-                  const double w1 = load_f64_agent(W1 + o), w2 = load_f64_agent(W2 + o);
-                  const double w3 = load_f64_agent(W3 + o), w4 = load_f64_agent(W4 + o);
-                  const double cn = w4 - ((c0 * (w2 - w1) + c1 * (w3 - w2)) + c2 * (w4 - w3));
-                  store_f64_agent(&dm[(size_t)s * n1 + k + 1], a_grid[k] + cn);   // AS:1499
-                  store_f64_agent(&dc[(size_t)s * n1 + k + 1], cn);
-                }
-              if (tid == 0) st.moved = 1;
-              if (!plain_barrier()) return;
-            }
-          }
-          ++n;
-        }
-        if (tid == 0) {
-          st.n = n;
-          if (!converged) st.status |= 1;
-        }
-        __syncthreads();
-        final_buf = st.buf[n & 1];
-        // an extrapolated solve that ended in NaN: the whole solve again, plain (ge.hip)
-        if (!(st.moved && st.nan_stop)) break;
-        if (tid == 0) {
-          st.extrap = 0;
-          st.status &= ~1;
-        }
-        __syncthreads();
-      }
+      const int final_buf = ge_household_solve<SMAX, SC, TH>(
+          cx, nb, ne, g, pk, R, secant ? cx.tabm(b_init) : (warm ? cx.tabm(b_cur) : nullptr),
+          secant ? cx.tabc(b_init) : (warm ? cx.tabc(b_cur) : nullptr));
+      if (final_buf < 0) return;
       if (tid == 0) {
         const unsigned long long tn = __builtin_amdgcn_s_memrealtime();
         st.t_egm += tn - tp;
@@ -756,22 +840,9 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
       __syncthreads();
       // ---- lottery of the own columns on the final tables (hist.hip hist_lottery_kernel) ----
       tp = __builtin_amdgcn_s_memrealtime();
-      ge_lottery_fn<SMAX, NW>(S, n_a, j0, j1, a_grid, tabm(st.buf[2]), tabc(st.buf[2]), R, st.steps > 0, LO, WL,
-                              g.pull != 0);
-      // ---- the distribution's start (own columns) ----
-      if (st.fresh_mass) {
-        const double u0 = 1.0 / ((double)S * n_a);
-        for (int s = 0; s < S; ++s)
-          for (int k = j0 + tid; k < j1; k += TH) X[(size_t)s * n_a + k] = u0;
-      } else if (warm) {
-        for (int s = 0; s < S; ++s)
-          for (int k = j0 + tid; k < j1; k += TH) {
-            const size_t o = (size_t)s * n_a + k;
-            const double x = X[o];
-            if (secant) X[o] = theta == 0.0 ? x : x + theta * (x - PX[o]);
-            PX[o] = x;
-          }
-      }
+      ge_lottery_fn<SMAX, NW>(S, n_a, j0, j1, cx.a_grid, cx.tabm(st.buf[2]), cx.tabc(st.buf[2]), R, st.ev.steps > 0,
+                              cx.LO, cx.WL, g.pull != 0);
+      ge_mass_start<TH>(cx, st.ev.fresh_mass != 0, warm, secant, theta);
       __syncthreads();
       if (tid == 0) {
         const unsigned long long tn = __builtin_amdgcn_s_memrealtime();
@@ -784,13 +855,13 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
     {
       HkArgs hk;
       hk.G = G; hk.S = S; hk.n_a = n_a; hk.cap = g.cap; hk.w = w; hk.j0 = j0; hk.j1 = j1;
-      hk.LO = to_global((const int*)LO); hk.WL = to_global((const double*)WL); hk.X = to_global(X);
+      hk.LO = to_global((const int*)cx.LO); hk.WL = to_global((const double*)cx.WL); hk.X = to_global(cx.X);
       hk.Pg = to_global(g.pg + row0); hk.Vg = to_global((double*)nullptr);
       hk.slab_cl = to_global(g.slab + (size_t)lc * G * 2 * g.cap);
       hk.span_cl = to_global(g.span + (size_t)lc * G * SMAX * 4);
-      hk.ctr = to_global(ctr); hk.gran = to_global(gran); hk.Pc = to_global(g.P + (size_t)cal * S * S);
+      hk.ctr = to_global(cx.ctr); hk.gran = to_global(cx.gran); hk.Pc = to_global(g.P + (size_t)cal * S * S);
       hk.max_iter = g.max_hist; hk.err = to_global(g.err);
-      hk.tol = st.htol;
+      hk.tol = st.ev.htol;
       hk.stop_ctr = to_global((const unsigned*)(g.stop_at > 0 ? g.done_ctr : nullptr));
       hk.stop_at = (unsigned)g.stop_at;
       hk.Qg = to_global(g.qb + row0);
@@ -816,55 +887,30 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
       break;
     }
     if (tid == 0) st.in_hist = 0;
-    // ---- K_s = sum mass a over the cluster ----
-    double part = 0.0;
-    for (int k = j0 + tid; k < j1; k += TH) {
-      double ms = 0.0;
-      for (int s = 0; s < S; ++s) ms += X[(size_t)s * n_a + k];
-      part += ms * a_grid[k];
-    }
-    {
-      double v[1] = {part};
-      if (!ge_reduce<TH>(gran, G, w, ne, v, 1, 0u, s_part, s_res, &s_flag, g.err)) return;
-    }
-    const bool fin = st.final_ks != 0;   // (set in an earlier pass; never cleared: the loop ends here)
+    if (!ge_capital<TH>(cx, ne, g.err)) return;
+    const bool fin = st.ev.final_ks != 0;   // (set in an earlier pass; never cleared: the loop ends here)
     if (tid == 0) {
-      const double Ks = s_res[0];
-      if (w == 0 && st.steps < kGeEvLog && !fin) {
-        double* ev = g.out_evlog + ((size_t)cal * kGeEvLog + st.steps) * kGeEvRec;
-        ev[0] = st.rs.x;
-        ev[1] = (Ks - st.Kd) / st.Kd;
+      const double Ks = ge_s_res[0];
+      if (w == 0 && st.ev.steps < kGeEvLog && !fin) {
+        double* ev = g.out_evlog + ((size_t)cal * kGeEvLog + st.ev.steps) * kGeEvRec;
+        ev[0] = st.ev.rs.x;
+        ev[1] = (Ks - st.ev.Kd) / st.ev.Kd;
         ev[2] = (double)st.n;
         ev[3] = (double)mv;
-        ev[4] = (double)st.loose;
+        ev[4] = (double)st.ev.loose;
         ev[5] = (double)(__builtin_amdgcn_s_memrealtime() - st.t_ev0) * 0.01;
       }
       st.its_sum += mv;
       if (mv >= g.max_hist) st.status |= 2;
     }
     if (fin) {   // the full-tolerance re-solve of the last evaluation: K_s only
-      if (tid == 0) st.Ks = s_res[0];
+      if (tid == 0) st.Ks = ge_s_res[0];
       __syncthreads();
       break;
     }
     if (tid == 0) {
-      const double Ks = s_res[0];
-      st.r_prev = st.r_cur;
-      st.r_cur = st.rs.x;
-      const double f = Ks - st.Kd;
-      st.refine = (st.loose && !(fabs(f) >= kGeSignMargin * st.Kd)) ||   // NaN: refine
-                  (st.adapt && !(fabs(f) >= kGeAdaptMargin * st.htol * st.Kd));
-      if (!st.refine) {
-        st.rs.update(f, st.Kd);
-        st.fmin = fmin(st.fmin, fabs(f) / st.Kd);
-      }
-      st.Ks = Ks;
-      ++st.steps;
-      // a search that ends on an evaluation at looser tolerances (a loose bracketing
-      // one, or Brent's at the adaptive distribution tolerance) reports K_s only after that r is
-      // evaluated again at egm_tol / hist_tol (one more pass, warm from its tables and mass: a few
-      // cycles and matvecs; searches normally end on full-tolerance evaluations near the root)
-      if (st.rs.done && (st.adapt || st.loose)) st.final_ks = 1;
+      st.ev.accept(ge_s_res[0]);
+      st.Ks = ge_s_res[0];
       st.t_k += __builtin_amdgcn_s_memrealtime() - tp;
     }
     __syncthreads();
@@ -877,27 +923,7 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
     }
     return;
   }
-  if (w == 0 && tid == 0) {
-    __hip_atomic_fetch_add(to_global(g.done_ctr), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    g.out_done[cal] = 1;
-    const double r = st.rs.x, a = cd.alpha, d = cd.delta;
-    g.out_r[cal] = r;
-    g.out_K[cal] = pow(a / (r + d), 1.0 / (1.0 - a));
-    g.out_Ks[cal] = st.Ks;
-    g.out_steps[cal] = st.steps;
-    g.out_cyc[cal] = (int)min(st.cyc_sum, 0x7fffffffll);
-    g.out_its[cal] = (int)min(st.its_sum, 0x7fffffffll);
-    g.out_status[cal] = st.status | (st.rs.done ? 0 : 4);
-    double* pf = g.out_prof + (size_t)cal * kGeProf;
-    pf[0] = st.t_egm * 0.01;
-    pf[1] = st.t_lot * 0.01;
-    pf[2] = st.t_hist * 0.01;
-    pf[3] = st.t_k * 0.01;
-    pf[4] = (__builtin_amdgcn_s_memrealtime() - st.t0) * 0.01;
-    pf[5] = (double)st.cyc_sum;
-    pf[6] = (double)st.its_sum;
-    pf[7] = (double)st.steps;
-  }
+  if (w == 0 && tid == 0) ge_write_out(cx, g, cd);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1022,8 +1048,8 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
     cals[c].alpha = M->alpha[c];
     cals[c].delta = M->delta[c];
     cals[c].disc = M->disc[c];
-    cals[c].r_lo = o->r_lo ? o->r_lo[c] : -0.5 * M->delta[c];
-    cals[c].r_hi = o->r_hi ? o->r_hi[c] : 1.0 / M->disc[c] - 1.0 - 1e-9;
+    cals[c].r_lo = o->r_lo ? o->r_lo[c] : GeEval::default_lo(M->delta[c]);
+    cals[c].r_hi = o->r_hi ? o->r_hi[c] : GeEval::default_hi(M->disc[c]);
   }
   GeRun g;
   g.n_cal = n_cal; g.S = S; g.n_a = n_a;

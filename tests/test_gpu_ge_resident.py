@@ -61,6 +61,48 @@ def test_resident_matches_host_search(gpu, method):
     assert np.max(np.abs(res.KtoY - ref.KtoY) / ref.KtoY) <= 2e-6
 
 
+def test_two_columns_per_thread_small_shape(gpu):
+    """The two-columns-per-thread kernel (the first, 24-cell launch of the full-size sweep) at a
+    small shape: clusters capped at 2 workgroups put 750 columns on each 512-thread workgroup."""
+    from aiyagari_hark_amd import _lib
+    from aiyagari_hark_amd.stationary import resident_plan, solve_table2
+    h = _lib.handle(gpu.index)
+    cals = _cells(4)
+    kw = dict(n_a=1500, device=gpu, method="brent", groups=1)
+    prev = h.set_options({_lib.AIY_OPT_HIST_CLUSTER: 2})
+    try:
+        plan = resident_plan(gpu, len(cals), 7, 1500)
+        res = solve_table2(cals, resident=True, **kw)
+    finally:
+        h.set_options(prev)
+    ref = solve_table2(cals, resident=False, **kw)
+    print(f"\nplan {plan}; resident r {res.r}; host r {ref.r}; max |dr| {np.max(np.abs(res.r - ref.r)):.2e}")
+    assert plan is not None and plan[:3] == (2, 750, 2)
+    assert np.all(res.status == 0) and np.all(ref.status == 0)
+    assert np.max(np.abs(res.r - ref.r)) <= 2e-7
+
+
+@pytest.mark.parametrize("anderson", [0, 12])
+def test_egm_acceleration_arms_match_host_search(gpu, anderson):
+    """The household solves' two accelerations, on both paths: AIY_OPT_GE_ANDERSON = 0 runs the
+    geometric extrapolation (ge_search.h egm_extrap_factor), 12 the Anderson mixing (aa_*)."""
+    from aiyagari_hark_amd import _lib
+    from aiyagari_hark_amd.stationary import solve_table2
+    h = _lib.handle(gpu.index)
+    cals = _cells(4)
+    kw = dict(n_a=1500, device=gpu, method="brent", groups=1, extrapolate=True)
+    prev = h.set_options({_lib.AIY_OPT_GE_ANDERSON: anderson})
+    try:
+        res = solve_table2(cals, resident=True, **kw)
+        ref = solve_table2(cals, resident=False, **kw)
+    finally:
+        h.set_options(prev)
+    print(f"\nanderson {anderson}: EGM cycles resident {int(res.egm_cycles[0][0])} host {int(ref.egm_cycles[0][0])}; "
+          f"max |dr| {np.max(np.abs(res.r - ref.r)):.2e}")
+    assert np.all(res.status == 0) and np.all(ref.status == 0)
+    assert np.max(np.abs(res.r - ref.r)) <= 2e-7
+
+
 def test_resident_default_sweep_and_stats(gpu):
     """solve_table2(method="brent") takes the resident path by default; its launch is
     counted by aiy_ge_launch_stats (the bench's roofline source)."""
