@@ -8,7 +8,9 @@ kernels (``csrc/``, built into ``lib/libaiyagari.so`` and called through the C A
 The reference's call surface lives in :mod:`aiyagari_hark_amd.model`
 (``AiyagariType``, ``AiyagariEconomy``); the batched stationary extensions (GE
 bisection on r, Young-lottery histogram, Rouwenhorst) in
-:mod:`aiyagari_hark_amd.stationary`.
+:mod:`aiyagari_hark_amd.stationary`; perfect-foresight transition paths after a shock
+(``steady_state``, ``household_block``, ``solve_transition``) in
+:mod:`aiyagari_hark_amd.transition`.
 """
 from __future__ import annotations
 
@@ -21,4 +23,7 @@ def __getattr__(name):
                 "init_Aiyagari_agents", "init_Aiyagari_economy"):
         from . import model
         return getattr(model, name)
+    if name in ("steady_state", "household_block", "solve_transition", "TransitionResult"):
+        from . import transition
+        return getattr(transition, name)
     raise AttributeError(name)

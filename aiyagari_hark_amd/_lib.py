@@ -81,6 +81,11 @@ class StationaryModel(ctypes.Structure):
                [(n, vp) for n in ("a_grid", "P", "lab", "beta", "crra", "alpha", "delta", "disc")]
 
 
+class TransitionModel(ctypes.Structure):
+    _fields_ = [("n_cal", ctypes.c_int32), ("S", ctypes.c_int32), ("n_a", ctypes.c_int32), ("T", ctypes.c_int32)] + \
+               [(n, vp) for n in ("a_grid", "P", "lab", "beta", "crra", "R", "w", "m_term", "c_term")]
+
+
 class GeOptions(ctypes.Structure):
     _fields_ = [("method", ctypes.c_int32), ("r_tol", ctypes.c_double), ("egm_tol", ctypes.c_double),
                 ("hist_tol", ctypes.c_double), ("max_steps", ctypes.c_int32), ("max_egm_cycles", ctypes.c_int32),
@@ -157,6 +162,10 @@ SIGNATURES = {
     "aiy_ge_stationary_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "aiy_ge_stationary": (ctypes.c_int32, [vp, ctypes.POINTER(StationaryModel), ctypes.POINTER(GeOptions), vp,
                                            c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, vp]),
+    "aiy_transition_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "aiy_transition_backward": (ctypes.c_int32, [vp, ctypes.POINTER(TransitionModel), vp, vp, vp, vp, vp, vp]),
+    "aiy_transition_forward": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                vp, vp, vp, vp, vp, vp, vp, vp, vp, c_double_p, c_double_p, vp]),
     "aiy_wealth_stats": (ctypes.c_int32, [vp, vp, vp, ctypes.c_int64, c_double_p, ctypes.c_int32, c_double_p,
                                           c_double_p, vp]),
 }

@@ -525,6 +525,52 @@ int32_t aiy_ge_last_rounds(aiy_handle* h, int32_t* launches, int32_t* mid_solve_
  * their stream) and their number.  reset != 0 zeroes the counters.  Host-only. */
 int32_t aiy_hist_launch_stats(aiy_handle* h, double* ms_sum, int64_t* launches, int32_t reset);
 
+/* ------------- perfect-foresight transition paths (build-defined) ------------- */
+
+/* A batch of stationary households on a price path of T + 1 periods: the device arrays of
+ * aiy_stationary_model, the path prices and the policy of the last period. */
+typedef struct {
+  int32_t n_cal, S, n_a, T;
+  const double* a_grid;  /* [n_cal][n_a]  device                                          */
+  const double* P;       /* [n_cal][S][S] device                                          */
+  const double* lab;     /* [n_cal][S]    device                                          */
+  const double* beta;    /* [n_cal]       device                                          */
+  const double* crra;    /* [n_cal]       device                                          */
+  const double* R;       /* [n_cal][T+1]  device: gross return of every period            */
+  const double* w;       /* [n_cal][T+1]  device: wage of every period                    */
+  const double* m_term;  /* [n_cal][S][n_a+1] device: policy of period T                  */
+  const double* c_term;  /* [n_cal][S][n_a+1] device                                      */
+} aiy_transition_model;
+
+/* Device scratch both transition calls need (caller-owned `work`; the two calls use
+ * disjoint parts of it), -1 for bad sizes (T < 1, n_a < 2, S outside 1..AIY_MAX_STATES).
+ * Host-only. */
+int64_t aiy_transition_work_bytes(int32_t n_cal, int32_t S, int32_t n_a, int32_t T);
+
+/* Backward sweep: for u = T .. 1, (m_{u-1}, c_{u-1}) = one aiy_egm_step (n_M = 1) from
+ * (m_u, c_u) with R[u], w[u] as next-period prices; lo[t], wlo[t] = aiy_hist_lottery of
+ * (m_t, c_t) at R[t], w[t] for t = 0 .. T-1, taken from the step's own interpolation
+ * (bit-identical to chaining the two entry points).  One launch per period, enqueued back
+ * to back.
+ *   lo / wlo: [T][n_cal][S][n_a] (caller-owned, device); m0_out / c0_out: [n_cal][S][n_a+1]
+ *   or both NULL.  Asynchronous. */
+int32_t aiy_transition_backward(aiy_handle* h, const aiy_transition_model* model, void* work, int32_t* lo,
+                                double* wlo, double* m0_out, double* c0_out, aiy_stream stream);
+
+/* Forward sweep: mass_{t+1} = lottery step of mass_t with (lo[t], wlo[t]) mixed by P, in pull
+ * form (no atomics; deterministic), t = 0 .. T-1, one launch per period.
+ *   mass [n_cal][S][n_a] device: in mass_0, out mass_T
+ *   Ks_out HOST [n_cal][T+1]: Ks[t] = sum mass_t a_grid
+ *   C_out  HOST [n_cal][T] or NULL: C[t] = sum mass_t (R[t] a + w[t] lab - a'), a' the
+ *          lottery's savings wlo a[lo] + (1 - wlo) a[lo + 1]; needs R, w (device
+ *          [n_cal][T+1]) and lab, which may be NULL with it.
+ * Returns AIY_ERR_UNSUPPORTED, with nothing pushed and Ks_out, C_out and mass untouched, if
+ * any row of lo is not non-decreasing or leaves [0, n_a - 2].  BLOCKING. */
+int32_t aiy_transition_forward(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
+                               const int32_t* lo, const double* wlo, const double* P, const double* a_grid,
+                               const double* R, const double* w, const double* lab, void* work, double* mass,
+                               double* Ks_out, double* C_out, aiy_stream stream);
+
 /* ------------------- wealth-distribution statistics ------------------- */
 
 /* HARK 0.12 get_lorenz_shares(data, weights, percentiles) and get_percentiles(...) of a
