@@ -9,7 +9,8 @@ The reference's call surface lives in :mod:`aiyagari_hark_amd.model`
 (``AiyagariType``, ``AiyagariEconomy``); the batched stationary extensions (GE
 bisection on r, Young-lottery histogram, Rouwenhorst) in
 :mod:`aiyagari_hark_amd.stationary`; perfect-foresight transition paths after a shock
-(``steady_state``, ``household_block``, ``solve_transition``) in
+(``steady_state``, ``household_block``, ``solve_transition``) and the sequence-space Jacobian
+of the household block (``household_jacobian``, ``impulse_response``) in
 :mod:`aiyagari_hark_amd.transition`.
 """
 from __future__ import annotations
@@ -23,7 +24,8 @@ def __getattr__(name):
                 "init_Aiyagari_agents", "init_Aiyagari_economy"):
         from . import model
         return getattr(model, name)
-    if name in ("steady_state", "household_block", "solve_transition", "TransitionResult"):
+    if name in ("steady_state", "household_block", "solve_transition", "TransitionResult", "household_jacobian",
+                "HouseholdJacobian", "impulse_response"):
         from . import transition
         return getattr(transition, name)
     raise AttributeError(name)

@@ -166,6 +166,14 @@ SIGNATURES = {
     "aiy_transition_backward": (ctypes.c_int32, [vp, ctypes.POINTER(TransitionModel), vp, vp, vp, vp, vp, vp]),
     "aiy_transition_forward": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                 vp, vp, vp, vp, vp, vp, vp, vp, vp, c_double_p, c_double_p, vp]),
+    "aiy_jacobian_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "aiy_jacobian_fanout": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp]),
+    "aiy_jacobian_diff": (ctypes.c_int32, [vp, ctypes.c_int64, vp, vp, ctypes.c_double, vp]),
+    "aiy_jacobian_expectation": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                  vp, vp, vp, vp, vp, vp, vp]),
+    "aiy_jacobian_contract": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               vp, vp, vp, vp, vp, vp]),
     "aiy_wealth_stats": (ctypes.c_int32, [vp, vp, vp, ctypes.c_int64, c_double_p, ctypes.c_int32, c_double_p,
                                           c_double_p, vp]),
 }

@@ -37,13 +37,11 @@
 #include "egm_common.h"
 #include "hist_cluster.h"
 #include "internal.h"
+#include "transition_common.h"
 
 #include <algorithm>
 
 namespace aiy {
-
-constexpr int kTrBlock = 256;
-constexpr int kTrWaves = kTrBlock / kWave;
 
 // ---------------------------------------------------------------------------------
 // Backward
@@ -297,7 +295,6 @@ static void launch_back(const TrBack& A, int n_cal, bool step, hipStream_t st) {
 // the [T n_cal S] rows (one thread per source j; j == n_a closes the row), and the row check.
 // A thread writes jb only between two entries it found in range, so a bad row writes nothing
 // out of bounds.
-constexpr int kTrRangePer = 4;   // sources per thread (one per thread: ~2 M tiny workgroups at Table II size)
 __global__ __launch_bounds__(kTrBlock) void tr_range_kernel(int S, int n_a, size_t r0, const int* __restrict__ lo,
                                                             int* __restrict__ jb, int* flag) {
   const size_t r = r0 + (size_t)blockIdx.z * S + blockIdx.y;
@@ -317,6 +314,27 @@ __global__ __launch_bounds__(kTrBlock) void tr_range_kernel(int S, int n_a, size
     }
     for (int d = prev + 1; d <= cur; ++d) J[d] = j;
   }
+}
+
+// The inverse index of every period of a lottery and its row check (transition_common.h).
+int32_t tr_build_ranges(aiy_handle* h, int n_cal, int S, int n_a, int T, const int* lo, int* jb, int* d_flag,
+                        hipStream_t st) {
+  AIY_HIP(h, hipMemsetAsync(d_flag, 0, sizeof(int), st));
+  const long long n_tc = (long long)T * n_cal;   // (period, calibration) pairs, <= 65535 per launch
+  for (long long z0 = 0; z0 < n_tc; z0 += 65535) {
+    const unsigned nz = (unsigned)std::min<long long>(65535, n_tc - z0);
+    const unsigned nx = (unsigned)((n_a + kTrBlock * kTrRangePer) / (kTrBlock * kTrRangePer));   // sources 0 .. n_a
+    hipLaunchKernelGGL(tr_range_kernel, dim3(nx, S, nz), dim3(kTrBlock), 0, st, S, n_a,
+                       (size_t)z0 * S, lo, jb, d_flag);
+  }
+  AIY_CHECK_LAUNCH(h);
+  int flag = 0;
+  AIY_HIP(h, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  AIY_HIP(h, hipStreamSynchronize(st));
+  if (flag != 0)
+    return fail(h, AIY_ERR_UNSUPPORTED,
+                "transition lottery check failed: a row of lo is not monotone (non-decreasing) or leaves [0, n_a - 2]");
+  return AIY_OK;
 }
 
 struct TrFwd {
@@ -343,9 +361,6 @@ __device__ __forceinline__ double tr_block_sum(double v, double* red) {
     for (int q = 0; q < kTrWaves; ++q) k += red[q];
   return k;
 }
-
-// A block owns kTrCols destination columns (one per lane); its waves share the states.
-constexpr int kTrCols = kWave;
 
 // Ks[0] = sum mass_0 a with the column partition of the forward step.
 __global__ __launch_bounds__(kTrBlock) void tr_K0_kernel(TrFwd A, const double* __restrict__ mass) {
@@ -497,8 +512,7 @@ struct TrLayout {
 };
 
 static bool tr_sizes_ok(int n_cal, int S, int n_a, int T) {
-  return n_cal >= 1 && n_cal <= 65535 && S >= 1 && S <= AIY_MAX_STATES && n_a >= 2 && T >= 1 &&
-         (long long)S * (n_a + 1) < 2147483647LL && n_a < 2147483647 - 2 * kTrBlock * kTrRangePer;
+  return tr_pull_sizes_ok(n_cal, S, n_a) && T >= 1;
 }
 
 static TrLayout tr_layout(int n_cal, int S, int n_a, int T) {
@@ -602,21 +616,8 @@ extern "C" int32_t aiy_transition_forward(aiy_handle* h, int32_t n_cal, int32_t 
   double* d_C = reinterpret_cast<double*>(wb + L.c);
   int* d_flag = reinterpret_cast<int*>(wb + L.flag);
   // inverse index of every period and the row check, before anything is pushed
-  AIY_HIP(h, hipMemsetAsync(d_flag, 0, sizeof(int), st));
-  const long long n_tc = (long long)T * n_cal;   // (period, calibration) pairs, <= 65535 per launch
-  for (long long z0 = 0; z0 < n_tc; z0 += 65535) {
-    const unsigned nz = (unsigned)std::min<long long>(65535, n_tc - z0);
-    const unsigned nx = (unsigned)((n_a + kTrBlock * kTrRangePer) / (kTrBlock * kTrRangePer));   // sources 0 .. n_a
-    hipLaunchKernelGGL(tr_range_kernel, dim3(nx, S, nz), dim3(kTrBlock), 0, st, S, n_a,
-                       (size_t)z0 * S, lo, jb, d_flag);
-  }
-  AIY_CHECK_LAUNCH(h);
-  int flag = 0;
-  AIY_HIP(h, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  AIY_HIP(h, hipStreamSynchronize(st));
-  if (flag != 0)
-    return fail(h, AIY_ERR_UNSUPPORTED,
-                "transition lottery check failed: a row of lo is not monotone (non-decreasing) or leaves [0, n_a - 2]");
+  rc = tr_build_ranges(h, n_cal, S, n_a, T, lo, jb, d_flag, st);
+  if (rc) return rc;
   TrFwd A;
   A.n_cal = n_cal; A.S = S; A.n_a = n_a; A.T = T; A.nblk = L.nblk;
   A.wlo = wlo; A.jb = jb; A.P = P; A.a_grid = a_grid; A.R = R; A.w = w; A.lab = lab;

@@ -15,8 +15,14 @@ given by the initial distribution.  One evaluation ``Ks(K)`` is ``household_bloc
     forward   mass_{t+1} = lottery step of mass_t, Ks[t] = sum mass_t a,
               C[t] = sum mass_t (q_t - a'_t)  (aiy_transition_forward).
 
+``method="newton"`` replaces the damping by a quasi-Newton step on the whole path with the
+sequence-space Jacobian of the block at the steady state (``household_jacobian``, the
+fake-news algorithm of Auclert, Bardoczy, Rognlie and Straub 2021; DESIGN.md §4i,
+csrc/transition_jac.hip); the same matrices give ``impulse_response``, the linear response
+to a TFP path.
+
 Everything per grid point runs in libaiyagari, batched over calibrations; the host only
-prices the path and damps it.  Several GPUs: split the calibrations with
+prices the path and updates it (damping, or one T x T solve per calibration).  Several GPUs: split the calibrations with
 ``parallel.split_calibrations`` and solve each share on its device -- the calibrations of
 a batch never interact.
 """
@@ -24,6 +30,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import time
 from dataclasses import dataclass
 
 import numpy as np
@@ -31,7 +38,7 @@ import torch
 
 from . import _lib
 from . import setup_math as sm
-from .stationary import StationaryBatch, _resolve_device, solve_table2
+from .stationary import StationaryBatch, _resolve_device, firm_prices, solve_table2
 
 F64 = torch.float64
 
@@ -188,7 +195,8 @@ class TransitionResult:
     status: np.ndarray       # [n_cal] 0: converged; bit 1: stopped at max_iter
 
 
-def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=None, m_term=None, c_term=None):
+def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=None, m_term=None, c_term=None,
+                     method="damped", jacobian=None):
     """Equilibrium capital path of every calibration of ``batch`` after the TFP path Z
     ([T+1] or [n_cal][T+1], Z[T] = 1), from the distribution mass0 (default: batch.mass, the
     steady state) to the terminal policy (default: batch.last_tables).
@@ -196,9 +204,19 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
     K starts at K[0] = sum mass0 a in every period; each iteration evaluates the household
     block on K's prices and moves K <- (1 - damping) K + damping Ks with K[0] held.  A
     calibration stops, and its path is no longer updated, once max_t |Ks_t - K_t| / K[0] < tol;
-    one still running after max_iter evaluations gets status bit 1 (nothing is raised)."""
+    one still running after max_iter evaluations gets status bit 1 (nothing is raised).
+
+    method="newton" keeps the start, the stop test, the frozen calibrations and the status and
+    replaces the update by K[1:] -= H^-1 (Ks[1:] - K[1:]), H the capital map of the household
+    Jacobian at the steady state of ``batch`` (``jacobian``: a HouseholdJacobian of this batch
+    and T to reuse, else one is built at r* = alpha K*^(alpha - 1) - delta, K* = sum batch.mass a).
+    H is factorised once per calibration; ``damping`` is not used."""
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     T = int(T)
+    if method not in ("damped", "newton"):
+        raise ValueError(f"method must be 'damped' or 'newton', got {method!r}")
+    if method == "damped" and jacobian is not None:
+        raise ValueError("jacobian= is only used by method='newton'")
     Z = np.broadcast_to(np.asarray(Z, dtype=np.float64), (n_cal, T + 1))
     if m_term is None or c_term is None:
         if getattr(batch, "last_tables", None) is None:
@@ -211,6 +229,15 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
     mass0 = mass0.reshape(n_cal, S, n_a).clone()
     K0 = np.sum(mass0.cpu().numpy() * batch.aGrid[:, None, :], axis=(1, 2))
     K = np.repeat(K0[:, None], T + 1, axis=1)
+    newton = None
+    if method == "newton":
+        if jacobian is None:
+            Ks = np.sum(batch.mass.cpu().numpy() * batch.aGrid[:, None, :], axis=(1, 2))
+            rs, _ = path_prices(Ks[:, None], np.ones((n_cal, 1)), batch.alpha, batch.delta)
+            jacobian = household_jacobian(batch, rs[:, 0], T, m_term=m_term, c_term=c_term)
+        if jacobian.JR.shape != (n_cal, T, T + 1):
+            raise ValueError(f"jacobian holds {jacobian.JR.shape}, the solve needs {(n_cal, T, T + 1)}")
+        newton = jacobian.solver()
     buffers = TransitionBuffers(batch, T)
     active = np.ones(n_cal, dtype=bool)
     iterations = np.zeros(n_cal, dtype=np.int64)
@@ -230,6 +257,8 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
             C[c] = out.C[c]
             if res[c] < tol:
                 active[c] = False
+            elif newton is not None:
+                K[c, 1:] -= newton(c, out.Ks[c, 1:] - K[c, 1:])
             else:
                 K[c, 1:] = (1.0 - damping) * K[c, 1:] + damping * out.Ks[c, 1:]
         if not active.any():
@@ -239,3 +268,206 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
         r[active], w[active] = rn[active], wn[active]
     status = np.where(active, 1, 0).astype(np.int32)
     return TransitionResult(K=K, r=r, w=w, C=C, iterations=iterations, residual=residual, status=status)
+
+
+# -------------------------------------------------------------------------------------
+# Sequence-space Jacobian of the household block
+# -------------------------------------------------------------------------------------
+@dataclass
+class HouseholdJacobian:
+    JR: np.ndarray       # [n_cal][T][T+1]  d Ks[t+1] / d R_u
+    Jw: np.ndarray       # [n_cal][T][T+1]  d Ks[t+1] / d w_u
+    FR: np.ndarray       # [n_cal][T][T+1]  fake-news matrices F[t][s] = sum E_t dD_s
+    Fw: np.ndarray
+    h: float             # the step of the one-sided differences
+    K: np.ndarray        # [n_cal] K* = sum D* a
+    alpha: np.ndarray    # [n_cal]
+
+    def capital_map(self):
+        """H [n_cal][T][T] = J^R[:, 1:] R'(K*) + J^w[:, 1:] w'(K*) - I: the derivative of
+        Ks[1:] - K[1:] with respect to K[1:] at the steady state (Z = 1; K[0] is given)."""
+        T = self.JR.shape[1]
+        a, K = self.alpha[:, None, None], self.K[:, None, None]
+        dR = a * (a - 1.0) * K ** (a - 2.0)
+        dw = a * (1.0 - a) * K ** (a - 1.0)
+        return self.JR[:, :, 1:] * dR + self.Jw[:, :, 1:] * dw - np.eye(T)[None]
+
+    def solver(self):
+        """``solve(c, b) -> H_c^-1 b``; every H_c is LU-factorised once, on the host, one
+        calibration at a time (a calibration's solve does not depend on the batch)."""
+        H = self.capital_map()
+        lu = [torch.linalg.lu_factor(torch.from_numpy(np.ascontiguousarray(H[c]))) for c in range(H.shape[0])]
+
+        def solve(c, b):
+            b = np.asarray(b, dtype=np.float64)
+            x = torch.linalg.lu_solve(lu[c][0], lu[c][1], torch.from_numpy(np.ascontiguousarray(b)).reshape(-1, 1))
+            return x.reshape(b.shape).numpy()
+        return solve
+
+
+def jacobian_from_fake_news(F):
+    """J[..., t, u] = sum_{k = 0 .. min(t, u)} F[..., t - k, u - k]."""
+    J = np.array(F, dtype=np.float64)
+    for t in range(1, J.shape[-2]):
+        J[..., t, 1:] += J[..., t - 1, :-1]
+    return J
+
+
+class JacobianBuffers:
+    """Device buffers of one (batch, T) Jacobian.  At the Table II shape with T = 300 one
+    [T+1][n_cal][S][n_a] array is 4 GB: the ghost steps and the two inputs' shocked steps are
+    held at once (the differences are formed in place in the shocked ones, which are then the
+    contraction's operands), E is a fourth, and the backward sweeps of the ghost and of both
+    inputs share one set of lottery buffers (``TransitionBuffers`` of T + 1 periods)."""
+
+    def __init__(self, batch: StationaryBatch, T: int):
+        n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
+        hd = _lib.handle(batch.device.index)
+        nbytes = int(hd.lib.aiy_jacobian_work_bytes(n_cal, S, n_a, int(T)))
+        if nbytes < 0:
+            raise ValueError(f"Jacobian sizes not supported: n_cal={n_cal} S={S} n_a={n_a} T={T}")
+        dev = batch.device
+        self.T = int(T)
+        self.work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.sweep = TransitionBuffers(batch, self.T + 1)
+        self.ghost = torch.empty((self.T + 1, n_cal, S, n_a), dtype=F64, device=dev)
+        self.dD = [torch.empty_like(self.ghost), torch.empty_like(self.ghost)]   # R, w
+        self.E = torch.empty((self.T, n_cal, S, n_a), dtype=F64, device=dev)
+        self.lo = torch.empty((n_cal, S, n_a), dtype=torch.int32, device=dev)    # the steady lottery
+        self.wlo = torch.empty((n_cal, S, n_a), dtype=F64, device=dev)
+        self.F = torch.empty((n_cal, self.T, 2 * (self.T + 1)), dtype=F64, device=dev)
+
+
+def jacobian_fanout(batch, lo, wlo, mass, out, work, T, stream=None):
+    """aiy_jacobian_fanout: out[t] = lottery step of ``mass`` with (lo[t], wlo[t]) for every
+    period of the device lottery [n_t][n_cal][S][n_a] (n_t <= T + 1, ``work`` sized for T).
+    Raises AiyagariLibError (AIY_ERR_UNSUPPORTED) with ``out`` untouched when a row fails the
+    monotone / range check."""
+    n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
+    hd = _lib.handle(batch.device.index)
+    hd.check(hd.lib.aiy_jacobian_fanout(hd.h, n_cal, S, n_a, int(T), int(lo.shape[0]), _lib.ptr(lo), _lib.ptr(wlo),
+                                        _lib.ptr(batch.d_P), _lib.ptr(mass), _lib.ptr(work), _lib.ptr(out),
+                                        _lib.stream_ptr(stream)), "aiy_jacobian_fanout")
+    return out
+
+
+def jacobian_expectation(batch, lo, wlo, E, work, stream=None):
+    """aiy_jacobian_expectation: E[k] [T][n_cal][S][n_a] of the device lottery (lo, wlo)."""
+    n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
+    hd = _lib.handle(batch.device.index)
+    hd.check(hd.lib.aiy_jacobian_expectation(hd.h, n_cal, S, n_a, int(E.shape[0]), _lib.ptr(lo), _lib.ptr(wlo),
+                                             _lib.ptr(batch.d_P), _lib.ptr(batch.d_a), _lib.ptr(work), _lib.ptr(E),
+                                             _lib.stream_ptr(stream)), "aiy_jacobian_expectation")
+    return E
+
+
+def jacobian_contract(device, E, dD_R, dD_w, work, F=None, stream=None):
+    """aiy_jacobian_contract: F [n_cal][T][2(T+1)] (device) of E [T][n_cal][S][n_a] and the two
+    inputs' dD [T+1][n_cal][S][n_a]."""
+    T, n_cal, S, n_a = E.shape
+    hd = _lib.handle(device.index)
+    if F is None:
+        F = torch.empty((n_cal, T, 2 * (T + 1)), dtype=F64, device=E.device)
+    hd.check(hd.lib.aiy_jacobian_contract(hd.h, n_cal, S, n_a, T, _lib.ptr(E), _lib.ptr(dD_R), _lib.ptr(dD_w),
+                                          _lib.ptr(work), _lib.ptr(F), _lib.stream_ptr(stream)),
+             "aiy_jacobian_contract")
+    return F
+
+
+def household_jacobian(batch, r, T, h=1e-5, m_term=None, c_term=None, buffers=None, timings=None):
+    """Sequence-space Jacobian of the household block of every calibration of ``batch`` at its
+    steady state (interest rate ``r`` [n_cal], tables ``batch.last_tables``, mass ``batch.mass``)
+    by the fake-news algorithm: J^x[t][u] = d Ks[t+1] / d x_u for x in {R, w}, t < T, u <= T.
+
+    Three backward sweeps over T + 2 periods (a ghost on constant prices and one per input
+    with x[T] += h), one fan-out lottery step of the steady mass per sweep, T - 1 expectation
+    steps and one FP64 matrix-instruction contraction; the host only accumulates the fake-news
+    matrices along their diagonals.  ``timings``: a dict that receives the milliseconds of
+    every stage (each stage is then synchronised)."""
+    n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
+    T = int(T)
+    dev = batch.device
+    if m_term is None or c_term is None:
+        if getattr(batch, "last_tables", None) is None:
+            raise ValueError("no steady-state policy: run steady_state / capital_supply first or pass m_term, c_term")
+        m_term, c_term = batch.last_tables
+    m_term = _tables(m_term, n_cal, S, n_a)
+    c_term = _tables(c_term, n_cal, S, n_a)
+    r = np.broadcast_to(np.asarray(r, dtype=np.float64), (n_cal,))
+    w, _ = firm_prices(r, batch.alpha, batch.delta)
+    Rs = 1.0 + r
+    if buffers is None:
+        buffers = JacobianBuffers(batch, T)
+    elif buffers.T != T:
+        raise ValueError(f"buffers hold T={buffers.T}, asked for T={T}")
+    hd = _lib.handle(dev.index)
+    mass = batch.mass.reshape(n_cal, S, n_a)
+    t_last = [time.perf_counter()]
+
+    def stage(name):
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (now - t_last[0]) * 1e3
+            t_last[0] = now
+
+    def step_of_sweep(shock, out):
+        R = np.repeat(Rs[:, None], T + 2, axis=1)
+        W = np.repeat(np.asarray(w)[:, None], T + 2, axis=1)
+        if shock == "R":
+            R[:, T] += h
+        elif shock == "w":
+            W[:, T] += h
+        transition_backward(batch, torch.as_tensor(R).to(dev), torch.as_tensor(W).to(dev), m_term, c_term,
+                            buffers.sweep, export_policy=False)
+        stage("backward")
+        jacobian_fanout(batch, buffers.sweep.lo, buffers.sweep.wlo, mass, out, buffers.work, T)
+        stage("fanout")
+
+    if timings is not None:
+        torch.cuda.synchronize(dev)
+        t_last[0] = time.perf_counter()
+    step_of_sweep(None, buffers.ghost)
+    for x, name in enumerate(("R", "w")):
+        step_of_sweep(name, buffers.dD[x])
+        hd.check(hd.lib.aiy_jacobian_diff(hd.h, buffers.ghost.numel(), _lib.ptr(buffers.dD[x]),
+                                          _lib.ptr(buffers.ghost), float(h), _lib.stream_ptr()), "aiy_jacobian_diff")
+        stage("diff")
+    dR, dw = torch.as_tensor(Rs.copy()).to(dev), torch.as_tensor(np.ascontiguousarray(w)).to(dev)
+    hd.check(hd.lib.aiy_hist_lottery(hd.h, n_cal, S, n_a, _lib.ptr(m_term), _lib.ptr(c_term), _lib.ptr(batch.d_a),
+                                     _lib.ptr(dR), _lib.ptr(dw), _lib.ptr(batch.d_lab), _lib.ptr(buffers.lo),
+                                     _lib.ptr(buffers.wlo), _lib.stream_ptr()), "aiy_hist_lottery")
+    jacobian_expectation(batch, buffers.lo, buffers.wlo, buffers.E, buffers.work)
+    stage("expectation")
+    jacobian_contract(dev, buffers.E, buffers.dD[0], buffers.dD[1], buffers.work, F=buffers.F)
+    stage("contraction")
+    raw = buffers.F.cpu().numpy()
+    # column c of an input is the lottery period c: the shock is s = T - c periods ahead
+    FR = np.ascontiguousarray(raw[:, :, :T + 1][:, :, ::-1])
+    Fw = np.ascontiguousarray(raw[:, :, T + 1:][:, :, ::-1])
+    K = np.sum(mass.cpu().numpy() * batch.aGrid[:, None, :], axis=(1, 2))
+    jac = HouseholdJacobian(JR=jacobian_from_fake_news(FR), Jw=jacobian_from_fake_news(Fw), FR=FR, Fw=Fw, h=float(h),
+                            K=K, alpha=np.array(batch.alpha, dtype=np.float64))
+    stage("host")
+    return jac
+
+
+def impulse_response(batch, jac, dZ):
+    """Linear response (dK, dr, dw), each [n_cal][T+1], of the economy at the steady state of
+    ``batch`` to the TFP path 1 + dZ (dZ [T+1] or [n_cal][T+1]): dK[0] = 0,
+    dK[1:] = -H^-1 (J^R alpha K*^(alpha-1) + J^w (1 - alpha) K*^alpha) dZ, and the linearised
+    firm's dr, dw."""
+    n_cal, T = jac.JR.shape[0], jac.JR.shape[1]
+    if n_cal != len(batch.cals):
+        raise ValueError(f"jacobian holds {n_cal} calibrations, the batch {len(batch.cals)}")
+    dZ = np.broadcast_to(np.asarray(dZ, dtype=np.float64), (n_cal, T + 1))
+    solve = jac.solver()
+    a, K = jac.alpha, jac.K
+    rZ = a * K ** (a - 1.0)
+    wZ = (1.0 - a) * K ** a
+    dK = np.zeros((n_cal, T + 1))
+    for c in range(n_cal):
+        dK[c, 1:] = -solve(c, (jac.JR[c] * rZ[c] + jac.Jw[c] * wZ[c]) @ dZ[c])
+    dr = rZ[:, None] * dZ + (a * (a - 1.0) * K ** (a - 2.0))[:, None] * dK
+    dw = wZ[:, None] * dZ + (a * (1.0 - a) * K ** (a - 1.0))[:, None] * dK
+    return dK, dr, dw

@@ -571,6 +571,54 @@ int32_t aiy_transition_forward(aiy_handle* h, int32_t n_cal, int32_t S, int32_t 
                                const double* R, const double* w, const double* lab, void* work, double* mass,
                                double* Ks_out, double* C_out, aiy_stream stream);
 
+/* ------- sequence-space Jacobian of the household block (build-defined) ------- */
+
+/* The device stages of the fake-news algorithm at a steady state; the backward sweeps are
+ * aiy_transition_backward's over T + 2 periods.  All buffers are caller-owned device memory and
+ * every call is ordered on `stream`. */
+
+/* Device scratch of the three calls below for a Jacobian of T rows (the inverse index of
+ * T + 1 lottery periods, the expectation recursion's two mixed vectors and the contraction's
+ * partials), -1 for bad sizes (T < 1, n_a < 2, S outside 1..AIY_MAX_STATES).  Host-only. */
+int64_t aiy_jacobian_work_bytes(int32_t n_cal, int32_t S, int32_t n_a, int32_t T);
+
+/* Fan-out step: out[t] = lottery step of the ONE distribution `mass` with (lo[t], wlo[t]) mixed
+ * by P, for every period t < n_t (n_t <= T + 1, T the size `work` was asked for) in one launch;
+ * each out[t] has the bits of aiy_transition_forward with T = 1 on that period.
+ *   lo / wlo: [n_t][n_cal][S][n_a]; mass: [n_cal][S][n_a] (read only); out: [n_t][n_cal][S][n_a]
+ * Returns AIY_ERR_UNSUPPORTED, with nothing written to out, if any row of lo is not
+ * non-decreasing or leaves [0, n_a - 2].  Blocks on `stream` for that check; the step itself
+ * is asynchronous. */
+int32_t aiy_jacobian_fanout(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T, int32_t n_t,
+                            const int32_t* lo, const double* wlo, const double* P, const double* mass,
+                            void* work, double* out, aiy_stream stream);
+
+/* shocked[i] = (shocked[i] - ghost[i]) / step for i < n: the distribution responses, formed
+ * element by element before anything is summed.  Asynchronous. */
+int32_t aiy_jacobian_diff(aiy_handle* h, int64_t n, double* shocked, const double* ghost, double step,
+                          aiy_stream stream);
+
+/* Expectation vectors of the lottery (lo, wlo) [n_cal][S][n_a]: E_0[s][j] = a_grid[j],
+ * E_{k+1}[s][j] = wlo G[s][lo] + (1 - wlo) G[s][lo + 1], G[s][d] = sum_{s'} P[s, s'] E_k[s'][d]
+ * in ascending s' (the transpose of the lottery step), k = 0 .. T - 2; one launch per k.
+ *   E_out: [T][n_cal][S][n_a]
+ * The lottery passes aiy_jacobian_fanout's row check first (AIY_ERR_UNSUPPORTED, nothing
+ * written; blocks on `stream` for it). */
+int32_t aiy_jacobian_expectation(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
+                                 const int32_t* lo, const double* wlo, const double* P, const double* a_grid,
+                                 void* work, double* E_out, aiy_stream stream);
+
+/* Fake-news contraction on the f64 matrix instruction:
+ *   F_out[cal][t][c]         = sum_{s, j} E[t][cal][s][j] dD_R[c][cal][s][j]
+ *   F_out[cal][t][T + 1 + c] = sum_{s, j} E[t][cal][s][j] dD_w[c][cal][s][j],  t < T, c <= T,
+ * one pass over E for both.  The long index (s, j) is summed in chunks of a fixed length,
+ * the chunks in ascending order: the bits depend on neither the device nor the batch.
+ *   E: [T][n_cal][S][n_a]; dD_R / dD_w: [T+1][n_cal][S][n_a]; F_out: DEVICE [n_cal][T][2(T+1)]
+ * Asynchronous. */
+int32_t aiy_jacobian_contract(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T, const double* E,
+                              const double* dD_R, const double* dD_w, void* work, double* F_out,
+                              aiy_stream stream);
+
 /* ------------------- wealth-distribution statistics ------------------- */
 
 /* HARK 0.12 get_lorenz_shares(data, weights, percentiles) and get_percentiles(...) of a
