@@ -867,8 +867,9 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
       hk.Qg = to_global(g.qb + row0);
       hk.Ainv = to_global(g.ainv + (size_t)cal * S * (n_a + 1));
       hk.lottery_fresh = true;
-      mv = g.pull ? hk_solve_inlined<SMAX, KC, TH, true>(hk, &nb, &ne)
-                  : hk_solve_isolated<SMAX, KC, TH, false, (KC == 1 || kGeFuseAKc2) && kGeFuseA>(hk, &nb, &ne);
+      hk.dyn_lds = hk_lds_addr(ge_dyn);
+      mv = g.pull ? hk_solve_inlined<SMAX, KC, TH, true, false, SC>(hk, &nb, &ne)
+                  : hk_solve_isolated<SMAX, KC, TH, false, (KC == 1 || kGeFuseAKc2) && kGeFuseA, SC>(hk, &nb, &ne);
     }
     if (mv == -1) return;
     if (tid == 0) {

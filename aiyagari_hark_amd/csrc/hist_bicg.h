@@ -126,14 +126,29 @@ struct HkArgs {
   gptr<double> Qg;             // [S][n_a]
   gptr<int> Ainv;              // [S][n_a + 1]
   bool lottery_fresh;          // LO / WL written in this launch by other workgroups (sc1 loads)
+  // hk_solve_isolated: the LDS address of the caller's dynamic shared memory (hk_lds_addr).
+  // Declared in the callee, a non-kernel function, it is found through the module's dynamic-LDS
+  // table, and the compiler reloads that word from memory in front of almost every LDS access
+  // (228 scalar loads in the two-column loop, each with a wait that drains the LDS queue)
+  unsigned dyn_lds;
 };
+
+template <class T>
+using lptr = __attribute__((address_space(3))) T*;
+// the 32-bit LDS address of a __shared__ object, opaque to the compiler: handed on plainly,
+// interprocedural constant propagation puts the dynamic-LDS symbol back into the callee
+__device__ __forceinline__ unsigned hk_lds_addr(double* p) {
+  unsigned a = (unsigned)(size_t)(lptr<double>)p;
+  asm volatile("" : "+s"(a));
+  return a;
+}
 
 // Returns the matvecs of the solve, or -1 when the cluster stops (error word set: a
 // timeout, a span that does not fit, too many covering workgroups), or -(2 + matvecs) when
 // a rebalancing stop was requested (X holds the current iterate; a later solve restarts
 // from it).  nb / ne: the
 // cluster barriers / reductions passed so far in this launch (counted on).
-template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false>
+template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false, int SC = 0>
 __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC, TH>& L, unsigned& nb,
                                         unsigned& ne) {
   constexpr bool kVlds = SMAX <= 8;
@@ -155,7 +170,10 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
 
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1), wid = tid / kWave;
-  const int G = r.G, S = r.S, n_a = r.n_a, cap = r.cap;
+  // SC > 0: the state count at compile time (the resident search's Table II kernels, S == SMAX:
+  // no per-state branches or clamps); 0: r.S
+  static_assert(SC >= 0 && SC <= SMAX, "compile-time state count within SMAX");
+  const int G = r.G, S = SC > 0 ? SC : r.S, n_a = r.n_a, cap = r.cap;
   const int w = r.w;
   const int j0 = r.j0;
   const int j1 = r.j1;
@@ -748,6 +766,14 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   bool restart = true, first = true;
   double rho = 0.0, total0 = 0.0;
   auto own = [&](int jc, int k, int s) { return s < S && jc + k * TH < j1; };
+  // In the iteration's phases a thread's column is active or not as a whole: one predicate (one
+  // exec region) per column around its guarded points, not one per point; the per-thread partial
+  // sums keep their (column, state) order, and an inactive column's entries stay 0.0
+  auto col_act = [&](int jc, bool (&act)[KC]) {
+#pragma unroll
+    for (int k = 0; k < KC; ++k) act[k] = jc + k * TH < j1;
+  };
+  bool act[KC];
   unsigned seed = 0;   // shadow-residual choice; a stagnating solve restarts with the next one
   auto rh_at = [&](int jc, int k, int s) { return hk_rhat((unsigned)(s * n_a + jc + k * TH) + seed * 0x5BD1E995u); };
   double best = __builtin_inf();   // best recursive max|r| since the last restart, and when
@@ -871,14 +897,20 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
       // max, which no residual of a mass vector reaches); x's loads in flight across it (one
       // column per thread; with two, x is loaded after the matvec: its registers are full)
       jc = col();
+      col_act(jc, act);
       double rm = 0.0;
 #pragma unroll
-      for (int k = 0; k < KC; ++k)
+      for (int k = 0; k < KC; ++k) {
+        if (act[k]) {
 #pragma unroll
-        for (int s = 0; s < SMAX; ++s) {
-          if (own(jc, k, s)) rm = nan_max(rm, fabs(Vl[vidx(k, s)]));
-          if constexpr (KC == 1) xq[k][s] = X[min(s, S - 1) * n_a + min(jc + k * TH, n_a - 1)];
+          for (int s = 0; s < SMAX; ++s)
+            if (s < S) rm = nan_max(rm, fabs(Vl[vidx(k, s)]));
         }
+        if constexpr (KC == 1) {
+#pragma unroll
+          for (int s = 0; s < SMAX; ++s) xq[k][s] = X[min(s, S - 1) * n_a + min(jc + k * TH, n_a - 1)];
+        }
+      }
       part[0] = pu;
       part[1] = (r.stop_ctr != nullptr && tid == 0 && s_stop) ? kHkStopSentinel : rm;
       if (!matvec_r(pv, tv, part, 2, 2u)) return -1;
@@ -897,19 +929,25 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
       if (!matvec(pv, tv)) return -1;
       ++mv;
       jc = col();
+      col_act(jc, act);
       double rvv = 0.0, rm = 0.0;
 #pragma unroll
-      for (int k = 0; k < KC; ++k)
+      for (int k = 0; k < KC; ++k) {
 #pragma unroll
         for (int s = 0; s < SMAX; ++s) {
-          const double v = pv[k][s] - tv[k][s];
+          tv[k][s] = pv[k][s] - tv[k][s];   // v
           rv[k][s] = Vl[vidx(k, s)];
-          Vl[vidx(k, s)] = v;
-          if (own(jc, k, s)) {
-            rvv += rh_at(jc, k, s) * v;
-            rm = nan_max(rm, fabs(rv[k][s]));
-          }
+          Vl[vidx(k, s)] = tv[k][s];
         }
+        if (act[k]) {
+#pragma unroll
+          for (int s = 0; s < SMAX; ++s)
+            if (s < S) {
+              rvv += rh_at(jc, k, s) * tv[k][s];
+              rm = nan_max(rm, fabs(rv[k][s]));
+            }
+        }
+      }
       part[0] = rvv;
       // the stop request rides on the max|r| partial as a sentinel no residual of a mass vector
       // reaches (the cluster max is the same in every workgroup)
@@ -948,35 +986,43 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     }
     // x += alpha p; p -> HBM scratch; s = r - alpha v (in rv); t = s - T s (in tv)
     jc = col();
+    col_act(jc, act);
 #pragma unroll
-    for (int k = 0; k < KC; ++k)
+    for (int k = 0; k < KC; ++k) {
+      if (act[k]) {
 #pragma unroll
-      for (int s = 0; s < SMAX; ++s) {
-        if (own(jc, k, s)) {
-          const int g = s * n_a + jc + k * TH;
-          X[g] = xq[k][s] + alpha * pv[k][s];
-          Pg[g] = pv[k][s];
-        }
-        rv[k][s] -= alpha * Vl[vidx(k, s)];
+        for (int s = 0; s < SMAX; ++s)
+          if (s < S) {
+            const int g = s * n_a + jc + k * TH;
+            X[g] = xq[k][s] + alpha * pv[k][s];
+            Pg[g] = pv[k][s];
+          }
       }
+#pragma unroll
+      for (int s = 0; s < SMAX; ++s) rv[k][s] -= alpha * Vl[vidx(k, s)];
+    }
     if (!matvec(rv, tv)) return -1;
     ++mv;
     jc = col();
+    col_act(jc, act);
     double ts = 0.0, tt = 0.0, rs = 0.0, rt = 0.0, sm = 0.0;
 #pragma unroll
-    for (int k = 0; k < KC; ++k)
+    for (int k = 0; k < KC; ++k) {
 #pragma unroll
-      for (int s = 0; s < SMAX; ++s) {
-        tv[k][s] = rv[k][s] - tv[k][s];
-        if (own(jc, k, s)) {
-          const double h = rh_at(jc, k, s);
-          ts += tv[k][s] * rv[k][s];
-          tt += tv[k][s] * tv[k][s];
-          rs += h * rv[k][s];
-          rt += h * tv[k][s];
-          sm = nan_max(sm, fabs(rv[k][s]));
-        }
+      for (int s = 0; s < SMAX; ++s) tv[k][s] = rv[k][s] - tv[k][s];
+      if (act[k]) {
+#pragma unroll
+        for (int s = 0; s < SMAX; ++s)
+          if (s < S) {
+            const double h = rh_at(jc, k, s);
+            ts += tv[k][s] * rv[k][s];
+            tt += tv[k][s] * tv[k][s];
+            rs += h * rv[k][s];
+            rt += h * tv[k][s];
+            sm = nan_max(sm, fabs(rv[k][s]));
+          }
       }
+    }
     part[0] = ts;
     part[1] = tt;
     part[2] = rs;
@@ -1008,19 +1054,29 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     rho = rho2;
     // x += omega s; r = s - omega t; p = r + beta (p - omega v)
     jc = col();
+    col_act(jc, act);
     double pun = 0.0;
 #pragma unroll
-    for (int k = 0; k < KC; ++k)
+    for (int k = 0; k < KC; ++k) {
+      if (act[k]) {
+#pragma unroll
+        for (int s = 0; s < SMAX; ++s)
+          if (s < S) X[s * n_a + jc + k * TH] = xq[k][s] + omega * rv[k][s];
+      }
 #pragma unroll
       for (int s = 0; s < SMAX; ++s) {
-        const bool ow = own(jc, k, s);
-        if (ow) X[s * n_a + jc + k * TH] = xq[k][s] + omega * rv[k][s];
-        const double pold = ow ? pq[k][s] : 0.0;
+        const double pold = (act[k] && s < S) ? pq[k][s] : 0.0;
         rv[k][s] = rv[k][s] - omega * tv[k][s];
         pv[k][s] = rv[k][s] + beta * (pold - omega * Vl[vidx(k, s)]);
-        if constexpr (FUSEA && kUqPre)
-          if (ow) pun += uq[k][s] * pv[k][s];
       }
+      if constexpr (FUSEA && kUqPre) {
+        if (act[k]) {
+#pragma unroll
+          for (int s = 0; s < SMAX; ++s)
+            if (s < S) pun += uq[k][s] * pv[k][s];
+        }
+      }
+    }
     if constexpr (FUSEA && !kUqPre) {   // u read back beside the new p (every load before the first use)
       double ul[KC][SMAX];
 #pragma unroll
@@ -1046,14 +1102,45 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   return mv;
 }
 
+// The arguments of a non-kernel function arrive in VGPRs, where the compiler must take them for
+// per-lane values: every address built from them is vector arithmetic (a v_mul_lo_u32 per row
+// index, a 64-bit vector add per access), every `s < S` an exec-mask region, and the pointers
+// hold ~30 VGPRs that the Krylov vectors then spill around.  They are the same in every lane:
+// read into SGPRs once at entry.
+__device__ __forceinline__ int hk_uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
+template <class T>
+__device__ __forceinline__ gptr<T> hk_uni(gptr<T> p) {
+  const unsigned long long u = (unsigned long long)p;
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+  return (gptr<T>)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ HkArgs hk_uniform_args(const HkArgs& a) {
+  HkArgs u;
+  u.G = hk_uni(a.G); u.S = hk_uni(a.S); u.n_a = hk_uni(a.n_a); u.cap = hk_uni(a.cap);
+  u.w = hk_uni(a.w); u.j0 = hk_uni(a.j0); u.j1 = hk_uni(a.j1);
+  u.LO = hk_uni(a.LO); u.WL = hk_uni(a.WL); u.X = hk_uni(a.X); u.Pg = hk_uni(a.Pg); u.Vg = hk_uni(a.Vg);
+  u.slab_cl = hk_uni(a.slab_cl); u.span_cl = hk_uni(a.span_cl); u.ctr = hk_uni(a.ctr); u.gran = hk_uni(a.gran);
+  u.Pc = hk_uni(a.Pc);
+  u.tol = hk_uni(a.tol);
+  u.max_iter = hk_uni(a.max_iter);
+  u.err = hk_uni(a.err);
+  u.stop_ctr = hk_uni(a.stop_ctr);
+  u.stop_at = (unsigned)hk_uni((int)a.stop_at);
+  u.Qg = hk_uni(a.Qg); u.Ainv = hk_uni(a.Ainv);
+  u.lottery_fresh = hk_uni((int)a.lottery_fresh) != 0;
+  u.dyn_lds = (unsigned)hk_uni((int)a.dyn_lds);
+  return u;
+}
+
 // hk_solve as its own (not inlined) function with its LDS declared here: a caller that
 // carries a lot of live state of its own (ge_resident.hip's search loop) would otherwise
 // force the solve's registers into scratch; the call costs a few register saves per
-// solve.  The span buffer / v share the caller's dynamic LDS.
-template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false>
+// solve.  The span buffer / v share the caller's dynamic LDS (HkArgs::dyn_lds).
+template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false, int SC = 0>
 __device__ __noinline__ int hk_solve_isolated(HkArgs a, unsigned* nb_io, unsigned* ne_io);
 // the same body inlined into the caller (the pull form spilled more as a separate function)
-template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false>
+template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false, int SC = 0>
 __device__ __forceinline__ int hk_solve_inlined(HkArgs a, unsigned* nb_io, unsigned* ne_io) {
   extern __shared__ double hk_dyn_in[];
   __shared__ int s_base[SMAX];
@@ -1072,14 +1159,16 @@ __device__ __forceinline__ int hk_solve_inlined(HkArgs a, unsigned* nb_io, unsig
   HkShared<SMAX, KC, TH> L{hk_dyn_in, s_base, s_pub, &s_tot, s_cand, s_ncand, s_cinfo, s_P, s_part, s_res,
                                  &s_flag, &s_stop, s_ex, &s_nheavy, s_wcnt, s_heavy, s_hval, &s_rok};
   unsigned nb = *nb_io, ne = *ne_io;
-  const int mv = hk_solve<SMAX, KC, TH, PULL, FUSEA>(a, L, nb, ne);
+  const int mv = hk_solve<SMAX, KC, TH, PULL, FUSEA, SC>(a, L, nb, ne);
   *nb_io = nb;
   *ne_io = ne;
   return mv;
 }
-template <int SMAX, int KC, int TH, bool PULL, bool FUSEA>
+template <int SMAX, int KC, int TH, bool PULL, bool FUSEA, int SC>
 __device__ __noinline__ int hk_solve_isolated(HkArgs a, unsigned* nb_io, unsigned* ne_io) {
-  extern __shared__ double hk_dyn[];
+  // the caller's dynamic LDS by address (wave-uniform, one SGPR), typed LDS so that every access
+  // stays a ds_ instruction
+  double* hk_dyn = (double*)(lptr<double>)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)a.dyn_lds);
   __shared__ int s_base[SMAX];
   __shared__ int s_pub[2 * SMAX][2];
   __shared__ int s_tot;
@@ -1096,7 +1185,7 @@ __device__ __noinline__ int hk_solve_isolated(HkArgs a, unsigned* nb_io, unsigne
   HkShared<SMAX, KC, TH> L{hk_dyn, s_base, s_pub, &s_tot, s_cand, s_ncand, s_cinfo, s_P, s_part, s_res,
                                  &s_flag, &s_stop, s_ex, &s_nheavy, s_wcnt, s_heavy, s_hval, &s_rok};
   unsigned nb = *nb_io, ne = *ne_io;
-  const int mv = hk_solve<SMAX, KC, TH, PULL, FUSEA>(a, L, nb, ne);
+  const int mv = hk_solve<SMAX, KC, TH, PULL, FUSEA, SC>(hk_uniform_args(a), L, nb, ne);
   *nb_io = nb;
   *ne_io = ne;
   return mv;
