@@ -201,6 +201,9 @@ __device__ __forceinline__ double marg_u(double c, double gam) {
     return 1.0 / ((c2 * c2) * c);
   } else return pow(c, -gam);
 }
+// inv_marg<5> outside the f32 range: the f64 pow as a call, so that the inlined ocml pow (1.7 KB
+// of code per use) and its registers stay out of the loops that almost never take it
+__device__ __noinline__ inline double inv_marg5_cold(double E) { return pow(E, -0.2); }
 template <int PK>
 __device__ __forceinline__ double inv_marg(double E, double gam) {
   if constexpr (PK == 1) return 1.0 / E;
@@ -208,7 +211,7 @@ __device__ __forceinline__ double inv_marg(double E, double gam) {
   else if constexpr (PK == 5) {
     // y = E^(-1/5): f32 estimate, two Newton steps on y^-5 = E (y += y (1 - E y^5) / 5);
     // outside the f32 range (or NaN) the f64 pow
-    if (!(E > 1e-30 && E < 1e30)) return pow(E, -0.2);
+    if (!(E > 1e-30 && E < 1e30)) return inv_marg5_cold(E);
     double y = (double)powf((float)E, -0.2f);
 #pragma unroll
     for (int it = 0; it < 2; ++it) {

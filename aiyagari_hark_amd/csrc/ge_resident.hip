@@ -27,10 +27,12 @@
 //     K_s         sum mass a (cluster reduction); f = K_s - K_d; loose-bracketing sign test
 //   until the search is done; workgroup 0 writes r, K, K_s, the counts and the status.
 //
-// The kernel is one body (one register allocation): its phases -- ge_vote, ge_secant_tables,
-// ge_household_solve (ge_egm_dispatch, ge_extrapolate, ge_anderson), the lottery, ge_mass_start,
-// the BiCGSTAB call, ge_capital, ge_write_out -- are __forceinline__ functions over GeCtx and
-// the file-scope LDS.
+// The kernel's phases -- ge_vote, ge_secant_tables, the lottery, ge_mass_start, ge_capital,
+// ge_write_out -- are __forceinline__ functions over GeCtx and the file-scope LDS, one body with
+// one register allocation; its two solves are functions of their own, each with its own
+// allocation: the household solve (ge_household_isolated: ge_household_solve with the cycle of
+// one CRRA kind, ge_extrapolate, ge_anderson) and the push form of the BiCGSTAB solve
+// (hk_solve_isolated, hist_bicg.h).
 //
 // The launch ends when the slowest calibration's whole search ends (the host loop's launches
 // each waited for the slowest calibration of that step).  Workgroup placement: block b runs
@@ -110,7 +112,6 @@ struct GeRun {
   int aa_period;          // EGM Anderson mixing every aa_period cycles (0: off; AIY_OPT_GE_ANDERSON)
   double* aah;            // [n_cal][kGeAaHist][S][n_a] the last kGeAaHist EGM outputs (c, own nodes)
   int logsec;             // log-secant bracketing (AIY_OPT_GE_LOGSEC, with loose bracketing)
-  int pull;               // distribution solves by the lottery pull (AIY_OPT_HIST_PULL): deterministic
   double loose_hist;      // loose-bracketing histogram tolerance (AIY_OPT_GE_LOOSE_HIST)
   double* qb;             // [n_cal][S][n_a] pull form: the matvec input rows
   int* ainv;              // [n_cal][S][n_a + 1] pull form: inverse lottery
@@ -203,7 +204,6 @@ __device__ __forceinline__ void ge_rows_pass(int S, int n_a, int j0, int j1, con
     const int j = jr < j1 ? jr : j1 - 1;   // lanes past the range repeat the last column
     const double a = a_grid[j];
     int* hint = s_hint + tile * SMAX;
-    begin(tile, j);
     auto fetch = [&](int r, RowWin& wn) {
       const int rr = r < S ? r : S - 1;
       load_win<true>(src_m + (size_t)rr * n1, src_c + (size_t)rr * n1, n, win_base(hint[rr], n1), lane, wn);
@@ -237,6 +237,7 @@ __device__ __forceinline__ void ge_rows_pass(int S, int n_a, int j0, int j1, con
     RowWin a0, b0, a1, b1;
     fetch(0, a0);
     fetch(1, b0);
+    begin(tile, j);   // (its loads behind the first windows': they are needed last, in end())
 #pragma unroll 1
     for (int u = 0; 2 * u < S; u += 2) {
       fetch(2 * u + 2, a1);
@@ -305,15 +306,15 @@ __device__ __forceinline__ double ge_egm_cycle(int S, int n_a, int j0, int j1, c
   // outputs (phase 2)
   constexpr int NP = SC > 0 ? SC : SMAX;
   double pmv[NP], pcv[NP];
+  // (loaded whether or not the distance is tracked, rows past S clamped: behind a branch the
+  // compiler cannot count these loads, and the wait for the tile's node a, loaded before them,
+  // became a wait for all of them -- vmcnt(0) in front of the first window loads of every tile)
   auto begin = [&](int, int j) {
 #pragma unroll
     for (int s = 0; s < NP; ++s) {
-      pmv[s] = 0.0;
-      pcv[s] = 0.0;
-      if (track && s < S) {
-        pmv[s] = load_f64_agent(&src_m[(size_t)s * n1 + j + 1]);
-        pcv[s] = load_f64_agent(&src_c[(size_t)s * n1 + j + 1]);
-      }
+      const int rr = s < S ? s : S - 1;
+      pmv[s] = load_f64_agent(&src_m[(size_t)rr * n1 + j + 1]);
+      pcv[s] = load_f64_agent(&src_c[(size_t)rr * n1 + j + 1]);
     }
   };
   auto end = [&](int, int j, double a) {   // phase 2 (each lane reads its own V)
@@ -346,8 +347,9 @@ __device__ __forceinline__ double ge_egm_cycle(int S, int n_a, int j0, int j1, c
   return dmax;
 }
 
-// The kernel's LDS at file scope, so the phases of the search (__forceinline__ functions: the
-// kernel is one body with one register allocation) address it directly.
+// The kernel's LDS at file scope, so the phases of the search (__forceinline__ functions) and
+// ge_household_isolated address it directly: every kernel of this file reaches it, so it has one
+// fixed address in all of them (no lookup in the separate function).
 constexpr int kGeSmax = 8;    // the largest resident state count (Table II: 7)
 extern __shared__ double ge_dyn[];                 // histogram: span buffer + v; EGM: V tiles + windows
 __shared__ double ge_s_part[kHcRed][kGeWavesMax];
@@ -363,9 +365,9 @@ template <int SMAX, int SC, int PK, int NW>
 __device__ __forceinline__ double ge_egm_cycle_fn(int S, int n_a, int j0, int j1, const double* a_grid,
                                                const double* src_m, const double* src_c, double* dst_m,
                                                double* dst_c, bool track, double R, double beta, double gam,
-                                               double* ring) {
+                                               double* dyn, double* ring) {
   return ge_egm_cycle<SMAX, SC, PK, NW>(S, n_a, j0, j1, a_grid, src_m, src_c, dst_m, dst_c, track, R, beta, gam,
-                                        ge_s_Wl, ge_s_Pe, ge_s_hint, ge_dyn, ge_dyn + (size_t)NW * SMAX * kTile, ring);
+                                        ge_s_Wl, ge_s_Pe, ge_s_hint, dyn, dyn + (size_t)NW * SMAX * kTile, ring);
 }
 
 // lottery of the own columns on the final tables (hist.hip hist_lottery_kernel's arithmetic)
@@ -419,6 +421,8 @@ struct GeCtx {
   unsigned long long* cw;     // counting-barrier words
   unsigned long long* gran;
   const double* a_grid;
+  double* aah;            // the calibration's Anderson ring: kGeAaHist slots of [S][n_a]
+  unsigned* err;
   double beta, gam;
   size_t tab_sz;
   int j0, j1, w, G, S, n_a, cal, lc;
@@ -475,23 +479,6 @@ __device__ __forceinline__ void ge_secant_tables(const GeCtx& cx, int b_cur, int
   }
 }
 
-// one EGM cycle with the marginal utility of the calibration's CRRA (pk: 1, 3, 5, else general)
-template <int SMAX, int SC, int NW>
-__device__ __forceinline__ double ge_egm_dispatch(const GeCtx& cx, int pk, const double* sm, const double* sc, double* dm,
-                                                  double* dc, bool track, double R, double* ring) {
-  if (pk == 1)
-    return ge_egm_cycle_fn<SMAX, SC, 1, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, dm, dc, track, R, cx.beta,
-                                            cx.gam, ring);
-  if (pk == 3)
-    return ge_egm_cycle_fn<SMAX, SC, 3, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, dm, dc, track, R, cx.beta,
-                                            cx.gam, ring);
-  if (pk == 5)
-    return ge_egm_cycle_fn<SMAX, SC, 5, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, dm, dc, track, R, cx.beta,
-                                            cx.gam, ring);
-  return ge_egm_cycle_fn<SMAX, SC, 0, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, dm, dc, track, R, cx.beta,
-                                          cx.gam, ring);
-}
-
 // Geometric extrapolation at a check (ge_search.h egm_extrap_factor; egm.hip egm_extrap_kernel):
 // the tables of cycle n (b_dst) move along their change from cycle n - 1 (b_src), own nodes.
 template <int TH>
@@ -523,8 +510,8 @@ __device__ __forceinline__ bool ge_extrapolate(const GeCtx& cx, unsigned& nb, un
 }
 
 // slot of cycle c's c table in the Anderson ring
-__device__ __forceinline__ double* ge_ring(const GeCtx& cx, const GeRun& g, int c) {
-  return g.aah + ((size_t)cx.cal * kGeAaHist + (size_t)(c % kGeAaHist)) * cx.S * cx.n_a;
+__device__ __forceinline__ double* ge_ring(const GeCtx& cx, int c) {
+  return cx.aah + (size_t)(c % kGeAaHist) * cx.S * cx.n_a;
 }
 
 // Type-II Anderson mix (ge_search.h aa_*) over the plain chain w0 .. w4 = the outputs of cycles
@@ -533,15 +520,14 @@ __device__ __forceinline__ double* ge_ring(const GeCtx& cx, const GeRun& g, int 
 // x_{n+1} = w4 - dF gamma replaces the cycle's output (own nodes, m = a + c), visible to every
 // workgroup after a barrier.
 template <int TH>
-__device__ __forceinline__ bool ge_anderson(const GeCtx& cx, unsigned& nb, unsigned& ne, const GeRun& g, int n,
-                                            int b_dst) {
+__device__ __forceinline__ bool ge_anderson(const GeCtx& cx, unsigned& nb, unsigned& ne, int n, int b_dst) {
   static_assert(kGeAaM == 3 && kGeAaHist == 5, "the mixing is written for m = 3");
   const int tid = threadIdx.x, n1 = cx.n_a + 1;
-  const double* W0 = ge_ring(cx, g, n - 4);
-  const double* W1 = ge_ring(cx, g, n - 3);
-  const double* W2 = ge_ring(cx, g, n - 2);
-  const double* W3 = ge_ring(cx, g, n - 1);
-  const double* W4 = ge_ring(cx, g, n);
+  const double* W0 = ge_ring(cx, n - 4);
+  const double* W1 = ge_ring(cx, n - 3);
+  const double* W2 = ge_ring(cx, n - 2);
+  const double* W3 = ge_ring(cx, n - 1);
+  const double* W4 = ge_ring(cx, n);
   double gp[9];
   for (int q = 0; q < 9; ++q) gp[q] = 0.0;
   for (int s = 0; s < cx.S; ++s)
@@ -552,9 +538,9 @@ __device__ __forceinline__ bool ge_anderson(const GeCtx& cx, unsigned& nb, unsig
       aa_gram_add(w0, w1, w2, w3, w4, gp);
     }
   double gs[9], gam[3];
-  if (!ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, gp, 6, 0u, ge_s_part, ge_s_res, &ge_s_flag, g.err)) return false;
+  if (!ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, gp, 6, 0u, ge_s_part, ge_s_res, &ge_s_flag, cx.err)) return false;
   for (int q = 0; q < 6; ++q) gs[q] = ge_s_res[q];
-  if (!ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, gp + 6, 3, 0u, ge_s_part, ge_s_res, &ge_s_flag, g.err)) return false;
+  if (!ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, gp + 6, 3, 0u, ge_s_part, ge_s_res, &ge_s_flag, cx.err)) return false;
   for (int q = 0; q < 3; ++q) gs[6 + q] = ge_s_res[q];
   if (aa_solve(gs, gam)) {
     double* dm = cx.tabm(b_dst);
@@ -569,23 +555,39 @@ __device__ __forceinline__ bool ge_anderson(const GeCtx& cx, unsigned& nb, unsig
         store_f64_agent(&dc[(size_t)s * n1 + k + 1], cn);
       }
     if (tid == 0) ge_st.moved = 1;
-    if (!ge_barrier(cx, nb, g.err)) return false;
+    if (!ge_barrier(cx, nb, cx.err)) return false;
   }
   return true;
+}
+
+// the launch's settings the household solve reads (GeRun's)
+struct GeHhOpt {
+  int max_cyc, aa_period, extrap_period;
+};
+
+// Cycle n's output goes into the Anderson ring only where a mix will read it: the next mix is at
+// the first multiple N >= n of the period p and reads cycles N - kGeAaHist + 1 .. N, and it runs
+// only under ge_anderson's entry condition (ge_household_solve below: N >= p, which every such
+// N meets, and N >= kGeAaHist + 1).  At p = 12 that is 5 cycles of 12; a period below kGeAaHist
+// keeps every cycle.
+__device__ __forceinline__ bool ge_ring_wanted(int n, int p) {
+  const int ph = n % p;
+  const int mix = ph == 0 ? n : n + (p - ph);
+  return (ph == 0 || ph > p - kGeAaHist) && mix >= kGeAaHist + 1;
 }
 
 // The household solve ([HARK] solve_agent: cycles until the sup-norm change of the tables is
 // <= tol, NaN stops; cold -- init_m == nullptr -- cycle 1 from the terminal guess).  Returns
 // the buffer of the final tables, -1: a barrier timed out.
-template <int SMAX, int SC, int TH>
-__device__ __forceinline__ int ge_household_solve(const GeCtx& cx, unsigned& nb, unsigned& ne, const GeRun& g, int pk,
-                                                  double R, const double* init_m, const double* init_c) {
+template <int SMAX, int SC, int PK, int TH>
+__device__ __forceinline__ int ge_household_solve(const GeCtx& cx, unsigned& nb, unsigned& ne, const GeHhOpt& g,
+                                                  double R, const double* init_m, const double* init_c, double* dyn) {
   constexpr int NW = TH / kWave;
   GeState& st = ge_st;
   const int tid = threadIdx.x;
   int final_buf = -1;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (!ge_barrier(cx, nb, g.err)) return -1;   // every workgroup's start tables visible
+    if (!ge_barrier(cx, nb, cx.err)) return -1;   // every workgroup's start tables visible
     // Anderson mixing (the first attempt; a NaN after a mix reruns the solve plain) replaces
     // the geometric extrapolation
     const bool aa = g.aa_period > 0 && attempt == 0;
@@ -603,8 +605,9 @@ __device__ __forceinline__ int ge_household_solve(const GeCtx& cx, unsigned& nb,
       const double* sm = n == 1 ? init_m : cx.tabm(b_src);
       const double* sc = n == 1 ? init_c : cx.tabc(b_src);
       const bool track = n >= 2;
-      const double dl = ge_egm_dispatch<SMAX, SC, NW>(cx, pk, sm, sc, cx.tabm(b_dst), cx.tabc(b_dst), track, R,
-                                                      aa ? ge_ring(cx, g, n) : nullptr);
+      double* ring = aa && ge_ring_wanted(n, g.aa_period) ? ge_ring(cx, n) : nullptr;
+      const double dl = ge_egm_cycle_fn<SMAX, SC, PK, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, cx.tabm(b_dst),
+                                                          cx.tabc(b_dst), track, R, cx.beta, cx.gam, dyn, ring);
       // cluster distance: the value itself at the extrapolation checks (cycles 32k - 1,
       // 32k), else only its two facts (some part > tol; some part NaN) on a counting barrier
       const int xp = g.extrap_period;
@@ -613,7 +616,7 @@ __device__ __forceinline__ int ge_household_solve(const GeCtx& cx, unsigned& nb,
       bool go;
       if (want_value) {
         double v[1] = {dl};
-        if (!ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, v, 1, 1u, ge_s_part, ge_s_res, &ge_s_flag, g.err)) return -1;
+        if (!ge_reduce<TH>(cx.gran, cx.G, cx.w, ne, v, 1, 1u, ge_s_part, ge_s_res, &ge_s_flag, cx.err)) return -1;
         dclu = ge_s_res[0];
         go = dclu > st.ev.etol;   // NaN: stop (HARK: go = distance > tolerance)
         if (tid == 0) st.nan_stop = dclu != dclu;
@@ -627,7 +630,7 @@ __device__ __forceinline__ int ge_household_solve(const GeCtx& cx, unsigned& nb,
           for (int q = 1; q < TH / kWave; ++q) d = nan_max(d, ge_s_part[0][q]);
           flag = (d > st.ev.etol ? 1u : 0u) | (d != d ? (1u << 16) : 0u);
         }
-        if (!ge_vote(cx, g.err, flag, dlt)) return -1;
+        if (!ge_vote(cx, cx.err, flag, dlt)) return -1;
         if (tid == 0) {
           st.stop = (dlt & 0xffffu) == 0u || (dlt >> 16) != 0u;
           st.nan_stop = (dlt >> 16) != 0u;
@@ -641,12 +644,12 @@ __device__ __forceinline__ int ge_household_solve(const GeCtx& cx, unsigned& nb,
       }
       if (n >= last_allowed) break;
       if (want_value && (n % xp) == 0) {
-        if (!ge_extrapolate<TH>(cx, nb, g.err, b_dst, b_src, dclu, n)) return -1;
+        if (!ge_extrapolate<TH>(cx, nb, cx.err, b_dst, b_src, dclu, n)) return -1;
       } else if (want_value) {
         if (tid == 0) st.dist = dclu;
       }
       if (aa && n >= g.aa_period && n >= kGeAaHist + 1 && (n % g.aa_period) == 0) {
-        if (!ge_anderson<TH>(cx, nb, ne, g, n, b_dst)) return -1;
+        if (!ge_anderson<TH>(cx, nb, ne, n, b_dst)) return -1;
       }
       ++n;
     }
@@ -665,6 +668,51 @@ __device__ __forceinline__ int ge_household_solve(const GeCtx& cx, unsigned& nb,
     __syncthreads();
   }
   return final_buf;
+}
+
+// ge_household_solve as its own (not inlined) function, one per CRRA kind: inlined, the four
+// kinds' cycles, the lottery, the mixing and the search loop's live state shared one register
+// allocation, and its spills sat in the cycle's tile loop.  The boundary is
+// hk_solve_isolated's (hist_bicg.h, §4j): the arguments arrive in VGPRs and are read into SGPRs
+// once at entry, the pointers typed global; the dynamic LDS comes by its 32-bit address, so its
+// accesses stay ds_ instructions; the barrier / reduction counts go in and out by pointer.  The
+// function does not depend on the columns per thread: the kernels of one state count share it.
+struct GeHhArgs {
+  gptr<double> tab, aah;
+  gptr<unsigned> ctr, err;
+  gptr<unsigned long long> gran;
+  gptr<const double> a_grid, init_m, init_c;
+  double beta, gam, R;
+  int j0, j1, w, G, S, n_a;
+  GeHhOpt opt;
+  unsigned dyn_lds;   // hk_lds_addr(ge_dyn)
+};
+template <int SMAX, int SC, int PK, int TH>
+__device__ __noinline__ int ge_household_isolated(GeHhArgs a, unsigned* nb_io, unsigned* ne_io) {
+  double* dyn = (double*)(lptr<double>)(size_t)(unsigned)hk_uni((int)a.dyn_lds);
+  GeCtx cx;
+  cx.tab = (double*)hk_uni(a.tab);
+  cx.aah = (double*)hk_uni(a.aah);
+  cx.ctr = (unsigned*)hk_uni(a.ctr);
+  cx.cw = reinterpret_cast<unsigned long long*>(cx.ctr + 2);
+  cx.err = (unsigned*)hk_uni(a.err);
+  cx.gran = (unsigned long long*)hk_uni(a.gran);
+  cx.a_grid = (const double*)hk_uni(a.a_grid);
+  cx.X = cx.PX = cx.WL = nullptr;   // (the distribution's arrays: not the household solve's)
+  cx.LO = nullptr;
+  cx.beta = hk_uni(a.beta); cx.gam = hk_uni(a.gam);
+  cx.j0 = hk_uni(a.j0); cx.j1 = hk_uni(a.j1); cx.w = hk_uni(a.w); cx.G = hk_uni(a.G);
+  cx.S = SC > 0 ? SC : hk_uni(a.S);
+  cx.n_a = hk_uni(a.n_a);
+  cx.cal = cx.lc = 0;
+  cx.tab_sz = (size_t)cx.S * (cx.n_a + 1);
+  const GeHhOpt opt = {hk_uni(a.opt.max_cyc), hk_uni(a.opt.aa_period), hk_uni(a.opt.extrap_period)};
+  unsigned nb = *nb_io, ne = *ne_io;
+  const int fb = ge_household_solve<SMAX, SC, PK, TH>(cx, nb, ne, opt, hk_uni(a.R), (const double*)hk_uni(a.init_m),
+                                                     (const double*)hk_uni(a.init_c), dyn);
+  *nb_io = nb;
+  *ne_io = ne;
+  return fb;
 }
 
 // The distribution's start (own columns): uniform, or the last mass -- with a secant start its
@@ -726,7 +774,9 @@ __device__ __forceinline__ void ge_write_out(const GeCtx& cx, const GeRun& g, co
 
 // setup -> while the search is not over { stop vote; plan; household solve; lottery; mass
 // start; distribution solve; K_s; accept } -> save the stopped search, or write it out
-template <int SMAX, int SC, int KC, int TH>
+// PULL: the launch's distribution solves by the lottery pull (AIY_OPT_HIST_PULL, the same for every
+// cluster of a launch): each kernel carries one form of the solve.
+template <int SMAX, int SC, int KC, int TH, bool PULL>
 __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
   constexpr int NW = TH / kWave;
   static_assert(SMAX <= kGeSmax, "file-scope LDS sized for kGeSmax states");
@@ -757,6 +807,8 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
   cx.ctr = g.ctr + (size_t)lc * kHcCtrStride;
   cx.cw = reinterpret_cast<unsigned long long*>(cx.ctr + 2);
   cx.gran = g.gran + (size_t)lc * 2 * G * kHcRedRec;
+  cx.aah = g.aah + (size_t)cal * kGeAaHist * S * n_a;
+  cx.err = g.err;
   unsigned nb = 0, ne = 0;   // plain barriers / reductions passed (hk_solve counts on)
   const int pk = cx.gam == 1.0 ? 1 : (cx.gam == 3.0 ? 3 : (cx.gam == 5.0 ? 5 : 0));
 
@@ -820,9 +872,20 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
       if (secant) ge_secant_tables<TH>(cx, b_cur, b_prev, b_init, theta);
       // ---- the household solve ----
       tp = __builtin_amdgcn_s_memrealtime();
-      const int final_buf = ge_household_solve<SMAX, SC, TH>(
-          cx, nb, ne, g, pk, R, secant ? cx.tabm(b_init) : (warm ? cx.tabm(b_cur) : nullptr),
-          secant ? cx.tabc(b_init) : (warm ? cx.tabc(b_cur) : nullptr));
+      GeHhArgs ha;
+      ha.tab = to_global(cx.tab); ha.aah = to_global(cx.aah); ha.ctr = to_global(cx.ctr); ha.err = to_global(g.err);
+      ha.gran = to_global(cx.gran); ha.a_grid = to_global(cx.a_grid);
+      ha.init_m = to_global((const double*)(secant ? cx.tabm(b_init) : (warm ? cx.tabm(b_cur) : nullptr)));
+      ha.init_c = to_global((const double*)(secant ? cx.tabc(b_init) : (warm ? cx.tabc(b_cur) : nullptr)));
+      ha.beta = cx.beta; ha.gam = cx.gam; ha.R = R;
+      ha.j0 = j0; ha.j1 = j1; ha.w = w; ha.G = G; ha.S = S; ha.n_a = n_a;
+      ha.opt = {g.max_cyc, g.aa_period, g.extrap_period};
+      ha.dyn_lds = hk_lds_addr(ge_dyn);
+      // one instantiation per CRRA kind (1, 3, 5, else the general pow), each with one copy of the cycle
+      const int final_buf = pk == 1   ? ge_household_isolated<SMAX, SC, 1, TH>(ha, &nb, &ne)
+                            : pk == 3 ? ge_household_isolated<SMAX, SC, 3, TH>(ha, &nb, &ne)
+                            : pk == 5 ? ge_household_isolated<SMAX, SC, 5, TH>(ha, &nb, &ne)
+                                      : ge_household_isolated<SMAX, SC, 0, TH>(ha, &nb, &ne);
       if (final_buf < 0) return;
       if (tid == 0) {
         const unsigned long long tn = __builtin_amdgcn_s_memrealtime();
@@ -841,7 +904,7 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
       // ---- lottery of the own columns on the final tables (hist.hip hist_lottery_kernel) ----
       tp = __builtin_amdgcn_s_memrealtime();
       ge_lottery_fn<SMAX, NW>(S, n_a, j0, j1, cx.a_grid, cx.tabm(st.buf[2]), cx.tabc(st.buf[2]), R, st.ev.steps > 0,
-                              cx.LO, cx.WL, g.pull != 0);
+                              cx.LO, cx.WL, PULL);
       ge_mass_start<TH>(cx, st.ev.fresh_mass != 0, warm, secant, theta);
       __syncthreads();
       if (tid == 0) {
@@ -868,8 +931,8 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
       hk.Ainv = to_global(g.ainv + (size_t)cal * S * (n_a + 1));
       hk.lottery_fresh = true;
       hk.dyn_lds = hk_lds_addr(ge_dyn);
-      mv = g.pull ? hk_solve_inlined<SMAX, KC, TH, true, false, SC>(hk, &nb, &ne)
-                  : hk_solve_isolated<SMAX, KC, TH, false, (KC == 1 || kGeFuseAKc2) && kGeFuseA, SC>(hk, &nb, &ne);
+      if constexpr (PULL) mv = hk_solve_inlined<SMAX, KC, TH, true, false, SC>(hk, &nb, &ne);
+      else mv = hk_solve_isolated<SMAX, KC, TH, false, (KC == 1 || kGeFuseAKc2) && kGeFuseA, SC>(hk, &nb, &ne);
     }
     if (mv == -1) return;
     if (tid == 0) {
@@ -937,8 +1000,9 @@ struct GePlan {
 };
 
 template <int SMAX, int SC, int KC, int TH>
-static const void* ge_fn() {
-  return reinterpret_cast<const void*>(ge_cluster_kernel<SMAX, SC, KC, TH>);
+static const void* ge_fn(bool pull) {
+  return pull ? reinterpret_cast<const void*>(ge_cluster_kernel<SMAX, SC, KC, TH, true>)
+              : reinterpret_cast<const void*>(ge_cluster_kernel<SMAX, SC, KC, TH, false>);
 }
 
 // Launch shape of the device-resident search for (n_cal, S, n_a): every calibration's
@@ -964,8 +1028,9 @@ static bool ge_make_plan(aiy_handle* h, int n_cal, int S, int n_a, GePlan& p) {
   p.kc = p.nj <= th ? 1 : 2;
   p.smax = S == 7 ? 7 : 8;   // the Table II shape: exact state count (fewer registers in the solve)
   p.sc = S == 7 ? 7 : 0;
-  if (p.sc == 7) p.fn = p.kc == 1 ? ge_fn<7, 7, 1, 512>() : ge_fn<7, 7, 2, 512>();
-  else p.fn = p.kc == 1 ? ge_fn<8, 0, 1, 512>() : ge_fn<8, 0, 2, 512>();
+  const bool pull = h->hist_pull != 0;   // AIY_OPT_HIST_PULL: deterministic distribution solves
+  if (p.sc == 7) p.fn = p.kc == 1 ? ge_fn<7, 7, 1, 512>(pull) : ge_fn<7, 7, 2, 512>(pull);
+  else p.fn = p.kc == 1 ? ge_fn<8, 0, 1, 512>(pull) : ge_fn<8, 0, 2, 512>(pull);
   hipFuncAttributes fa;
   if (hipFuncGetAttributes(&fa, p.fn) != hipSuccess) return false;
   int lds_dev = 0;
@@ -1072,7 +1137,6 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
   g.pg = reinterpret_cast<double*>(base + L.pg);
   g.qb = reinterpret_cast<double*>(base + L.qb);
   g.ainv = reinterpret_cast<int*>(base + L.ainv);
-  g.pull = h->hist_pull;
   g.loose_hist = std::pow(10.0, -(double)h->ge_loose_hist);
   g.lo = reinterpret_cast<int*>(base + L.lo);
   g.wlo = reinterpret_cast<double*>(base + L.wlo);
