@@ -11,7 +11,9 @@ bisection on r, Young-lottery histogram, Rouwenhorst) in
 :mod:`aiyagari_hark_amd.stationary`; perfect-foresight transition paths after a shock
 (``steady_state``, ``household_block``, ``solve_transition``) and the sequence-space Jacobian
 of the household block (``household_jacobian``, ``impulse_response``) in
-:mod:`aiyagari_hark_amd.transition`.
+:mod:`aiyagari_hark_amd.transition`; wealth statistics of the panel and of histogram
+distributions and paths (``histogram_stats``, ``batch_wealth_stats``, ``path_wealth_stats``) in
+:mod:`aiyagari_hark_amd.stats`.
 """
 from __future__ import annotations
 
@@ -25,7 +27,10 @@ def __getattr__(name):
         from . import model
         return getattr(model, name)
     if name in ("steady_state", "household_block", "solve_transition", "TransitionResult", "household_jacobian",
-                "HouseholdJacobian", "impulse_response"):
+                "HouseholdJacobian", "impulse_response", "path_wealth_stats"):
         from . import transition
         return getattr(transition, name)
+    if name in ("histogram_stats", "batch_wealth_stats", "WealthStats"):
+        from . import stats
+        return getattr(stats, name)
     raise AttributeError(name)

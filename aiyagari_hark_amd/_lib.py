@@ -166,6 +166,9 @@ SIGNATURES = {
     "aiy_transition_backward": (ctypes.c_int32, [vp, ctypes.POINTER(TransitionModel), vp, vp, vp, vp, vp, vp]),
     "aiy_transition_forward": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                 vp, vp, vp, vp, vp, vp, vp, vp, vp, c_double_p, c_double_p, vp]),
+    "aiy_transition_forward_marginals": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                          ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                          c_double_p, c_double_p, vp, vp]),
     "aiy_jacobian_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "aiy_jacobian_fanout": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp]),
@@ -176,6 +179,10 @@ SIGNATURES = {
                                                vp, vp, vp, vp, vp, vp]),
     "aiy_wealth_stats": (ctypes.c_int32, [vp, vp, vp, ctypes.c_int64, c_double_p, ctypes.c_int32, c_double_p,
                                           c_double_p, vp]),
+    "aiy_dist_stats_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
+    "aiy_dist_marginal": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
+    "aiy_dist_stats": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, c_double_p,
+                                        ctypes.c_int32, vp, c_double_p, c_double_p, c_double_p, vp]),
 }
 
 _lib = None

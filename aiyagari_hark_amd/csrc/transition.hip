@@ -32,6 +32,9 @@
 //                        [period][calibration][block]; tr_sum_kernel adds the blocks in block
 //                        order after the sweep (two fixed-order levels).
 //
+//   tr_marginal_kernel   (aiy_transition_forward_marginals only) the sum over s, ascending, of the
+//                        mass a period's step just wrote: thread = (calibration, node).
+//
 // Offsets into the [T][n_cal][S][n_a] arrays are size_t (24 x 300 x 7 x 10 000 > 2^31).
 #include "common.h"
 #include "egm_common.h"
@@ -502,6 +505,29 @@ static void launch_fwd(const TrFwd& A, int t, bool with_c, const double* src, do
   else hipLaunchKernelGGL((tr_forward_kernel<false>), grid, dim3(kTrBlock), 0, st, A, t, src, dst);
 }
 
+// g[dist][j] = ((mass[dist][0][j] + mass[dist][1][j]) + ...) + mass[dist][S - 1][j]: the marginal
+// over assets of a stack of [S][n_a] masses.  A thread owns one (distribution, node) and adds
+// its S values in ascending s; consecutive lanes own consecutive nodes.  No atomics.
+__global__ __launch_bounds__(kTrBlock) void tr_marginal_kernel(int S, int n_a, const double* __restrict__ mass,
+                                                               double* __restrict__ g) {
+  const int j = blockIdx.x * kTrBlock + threadIdx.x;
+  if (j >= n_a) return;
+  const double* m = mass + (size_t)blockIdx.y * S * n_a + j;
+  double v = m[0];
+  for (int s = 1; s < S; ++s) v += m[(size_t)s * n_a];
+  g[(size_t)blockIdx.y * n_a + j] = v;
+}
+
+// transition_common.h: the marginals of n_dist distributions, full width over nodes x distributions
+void tr_launch_marginal(long long n_dist, int S, int n_a, const double* mass, double* g, hipStream_t st) {
+  const unsigned nx = (unsigned)((n_a + kTrBlock - 1) / kTrBlock);
+  for (long long d0 = 0; d0 < n_dist; d0 += 65535) {   // grid.y <= 65535
+    const unsigned ny = (unsigned)std::min<long long>(65535, n_dist - d0);
+    hipLaunchKernelGGL(tr_marginal_kernel, dim3(nx, ny), dim3(kTrBlock), 0, st, S, n_a,
+                       mass + (size_t)d0 * S * n_a, g + (size_t)d0 * n_a);
+  }
+}
+
 // ---------------------------------------------------------------------------------
 // Work space (caller-owned): every region starts on a 256-byte boundary.
 // ---------------------------------------------------------------------------------
@@ -596,10 +622,12 @@ extern "C" int32_t aiy_transition_backward(aiy_handle* h, const aiy_transition_m
   return AIY_OK;
 }
 
-extern "C" int32_t aiy_transition_forward(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
-                                          const int32_t* lo, const double* wlo, const double* P, const double* a_grid,
-                                          const double* R, const double* w, const double* lab, void* work, double* mass,
-                                          double* Ks_out, double* C_out, aiy_stream stream) {
+// The forward sweep of aiy_transition_forward; with `marg` also the marginal of every period's
+// mass, [T + 1][n_cal][n_a], one tr_marginal_kernel launch behind the launch that wrote the mass.
+static int32_t tr_forward_sweep(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T, const int32_t* lo,
+                                const double* wlo, const double* P, const double* a_grid, const double* R,
+                                const double* w, const double* lab, void* work, double* mass, double* Ks_out,
+                                double* C_out, double* marg, aiy_stream stream) {
   if (!h) return AIY_ERR_ARG;
   int32_t rc = tr_check(h, n_cal, S, n_a, T);
   if (rc) return rc;
@@ -624,11 +652,14 @@ extern "C" int32_t aiy_transition_forward(aiy_handle* h, int32_t n_cal, int32_t 
   A.Kpart = reinterpret_cast<double*>(wb + L.kpart);
   A.Cpart = reinterpret_cast<double*>(wb + L.cpart);
   const bool with_c = C_out != nullptr;
+  const size_t per_marg = (size_t)n_cal * n_a;
   hipLaunchKernelGGL(tr_K0_kernel, dim3(L.nblk, n_cal), dim3(kTrBlock), 0, st, A, (const double*)mass);
+  if (marg) tr_launch_marginal(n_cal, S, n_a, mass, marg, st);
   for (int t = 0; t < T; ++t) {   // period t reads mass (t even) / alt (t odd)
     const double* src = (t & 1) ? alt : mass;
     double* dst = (t & 1) ? mass : alt;
     launch_fwd(A, t, with_c, src, dst, st);
+    if (marg) tr_launch_marginal(n_cal, S, n_a, dst, marg + (size_t)(t + 1) * per_marg, st);
   }
   const long long n_sum = (long long)(T + 1) * n_cal;
   hipLaunchKernelGGL(tr_sum_kernel, dim3((unsigned)((n_sum + 255) / 256)), dim3(256), 0, st, A, d_Ks,
@@ -640,4 +671,23 @@ extern "C" int32_t aiy_transition_forward(aiy_handle* h, int32_t n_cal, int32_t 
   if (with_c) AIY_HIP(h, hipMemcpyAsync(C_out, d_C, (size_t)n_cal * T * sizeof(double), hipMemcpyDeviceToHost, st));
   AIY_HIP(h, hipStreamSynchronize(st));
   return AIY_OK;
+}
+
+extern "C" int32_t aiy_transition_forward(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
+                                          const int32_t* lo, const double* wlo, const double* P, const double* a_grid,
+                                          const double* R, const double* w, const double* lab, void* work, double* mass,
+                                          double* Ks_out, double* C_out, aiy_stream stream) {
+  return tr_forward_sweep(h, n_cal, S, n_a, T, lo, wlo, P, a_grid, R, w, lab, work, mass, Ks_out, C_out, nullptr,
+                          stream);
+}
+
+extern "C" int32_t aiy_transition_forward_marginals(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
+                                                    const int32_t* lo, const double* wlo, const double* P,
+                                                    const double* a_grid, const double* R, const double* w,
+                                                    const double* lab, void* work, double* mass, double* Ks_out,
+                                                    double* C_out, double* marg_out, aiy_stream stream) {
+  if (!h) return AIY_ERR_ARG;
+  if (!marg_out) return fail(h, AIY_ERR_ARG, "null marg_out");
+  return tr_forward_sweep(h, n_cal, S, n_a, T, lo, wlo, P, a_grid, R, w, lab, work, mass, Ks_out, C_out, marg_out,
+                          stream);
 }

@@ -28,4 +28,8 @@ inline bool tr_pull_sizes_ok(int n_cal, int S, int n_a) {
 int32_t tr_build_ranges(aiy_handle* h, int n_cal, int S, int n_a, int T, const int* lo, int* jb, int* d_flag,
                         hipStream_t st);
 
+// g[d][j] = sum over s, ascending, of mass[d][s][j] for the n_dist distributions of a
+// [n_dist][S][n_a] stack (tr_marginal_kernel, transition.hip).  Asynchronous on `st`.
+void tr_launch_marginal(long long n_dist, int S, int n_a, const double* mass, double* g, hipStream_t st);
+
 }  // namespace aiy

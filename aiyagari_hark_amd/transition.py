@@ -38,6 +38,7 @@ import torch
 
 from . import _lib
 from . import setup_math as sm
+from . import stats as _stats
 from .stationary import StationaryBatch, _resolve_device, firm_prices, solve_table2
 
 F64 = torch.float64
@@ -101,13 +102,15 @@ class BlockResult:
     m0: torch.Tensor | None   # [n_cal][S][n_a+1] policy of period 0, device
     c0: torch.Tensor | None
     mass_T: torch.Tensor      # [n_cal][S][n_a] device
+    marg: torch.Tensor | None = None   # [T+1][n_cal][n_a] device: the marginal over assets of every period
 
 
 class TransitionBuffers:
     """Device buffers of one (batch, T): the lotteries, the work space and a mass scratch,
-    allocated once and reused by every block evaluation of a solve."""
+    allocated once and reused by every block evaluation of a solve.  ``marginals=True`` adds
+    the [T+1][n_cal][n_a] buffer of the period marginals (``household_block(marginals=True)``)."""
 
-    def __init__(self, batch: StationaryBatch, T: int):
+    def __init__(self, batch: StationaryBatch, T: int, marginals: bool = False):
         n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
         h = _lib.handle(batch.device.index)
         nbytes = int(h.lib.aiy_transition_work_bytes(n_cal, S, n_a, int(T)))
@@ -121,6 +124,7 @@ class TransitionBuffers:
         self.m0 = torch.empty((n_cal, S, n_a + 1), dtype=F64, device=dev)
         self.c0 = torch.empty((n_cal, S, n_a + 1), dtype=F64, device=dev)
         self.mass = torch.empty((n_cal, S, n_a), dtype=F64, device=dev)
+        self.marg = torch.empty((self.T + 1, n_cal, n_a), dtype=F64, device=dev) if marginals else None
 
 
 def transition_backward(batch, R, w, m_term, c_term, buffers, export_policy=True, stream=None):
@@ -137,30 +141,39 @@ def transition_backward(batch, R, w, m_term, c_term, buffers, export_policy=True
             "aiy_transition_backward")
 
 
-def transition_forward(batch, lo, wlo, mass, T, work, R=None, w=None, want_c=True, stream=None):
+def transition_forward(batch, lo, wlo, mass, T, work, R=None, w=None, want_c=True, stream=None, marg=None):
     """aiy_transition_forward on device lotteries [T][n_cal][S][n_a]: advances ``mass`` in
     place from period 0 to period T and returns (Ks [n_cal][T+1], C [n_cal][T] or None).
+    With ``marg`` (device [T+1][n_cal][n_a]) the sweep is aiy_transition_forward_marginals: the
+    same results, and marg[t] = the sum over states of mass_t, t = 0 .. T.
     Raises AiyagariLibError (AIY_ERR_UNSUPPORTED) when a lottery row fails the monotone /
-    range check; mass is then untouched."""
+    range check; mass (and marg) is then untouched."""
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     h = _lib.handle(batch.device.index)
     Ks = np.zeros((n_cal, T + 1))
     C = np.zeros((n_cal, T)) if want_c else None
-    h.check(h.lib.aiy_transition_forward(h.h, n_cal, S, n_a, int(T), _lib.ptr(lo), _lib.ptr(wlo), _lib.ptr(batch.d_P),
-                                         _lib.ptr(batch.d_a), _lib.ptr(R) if want_c else None,
-                                         _lib.ptr(w) if want_c else None, _lib.ptr(batch.d_lab) if want_c else None,
-                                         _lib.ptr(work), _lib.ptr(mass), Ks.ctypes.data_as(_lib.c_double_p),
-                                         C.ctypes.data_as(_lib.c_double_p) if want_c else None,
-                                         _lib.stream_ptr(stream)), "aiy_transition_forward")
+    args = (h.h, n_cal, S, n_a, int(T), _lib.ptr(lo), _lib.ptr(wlo), _lib.ptr(batch.d_P), _lib.ptr(batch.d_a),
+            _lib.ptr(R) if want_c else None, _lib.ptr(w) if want_c else None,
+            _lib.ptr(batch.d_lab) if want_c else None, _lib.ptr(work), _lib.ptr(mass),
+            Ks.ctypes.data_as(_lib.c_double_p), C.ctypes.data_as(_lib.c_double_p) if want_c else None)
+    if marg is None:
+        h.check(h.lib.aiy_transition_forward(*args, _lib.stream_ptr(stream)), "aiy_transition_forward")
+    else:
+        if tuple(marg.shape) != (T + 1, n_cal, n_a) or marg.dtype != F64:
+            raise ValueError(f"marg must be float64 [T+1][n_cal][n_a] = {(T + 1, n_cal, n_a)}, got {tuple(marg.shape)}")
+        h.check(h.lib.aiy_transition_forward_marginals(*args, _lib.ptr(marg), _lib.stream_ptr(stream)),
+                "aiy_transition_forward_marginals")
     return Ks, C
 
 
-def household_block(batch, R, w, m_term, c_term, mass0, want_c=True, export_policy=True, buffers=None, stream=None):
+def household_block(batch, R, w, m_term, c_term, mass0, want_c=True, export_policy=True, buffers=None, stream=None,
+                    marginals=False):
     """One household-block evaluation on the price paths R, w ([n_cal][T+1], NumPy or device):
     the backward sweep from the terminal policy (m_term, c_term), then the forward sweep from
     mass0 (left unchanged).  Returns BlockResult: Ks[n_cal][T+1], C[n_cal][T] and the device
     lotteries, period-0 policy and final mass (views of ``buffers``: the next evaluation with
-    the same buffers overwrites them)."""
+    the same buffers overwrites them).  ``marginals=True`` also returns ``marg`` [T+1][n_cal][n_a],
+    the marginal over assets of every period's mass (``path_wealth_stats`` reads it)."""
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     dev = batch.device
     dR = torch.as_tensor(np.ascontiguousarray(R, dtype=np.float64)).to(dev) if not torch.is_tensor(R) else R
@@ -169,9 +182,11 @@ def household_block(batch, R, w, m_term, c_term, mass0, want_c=True, export_poli
         raise ValueError(f"price paths must be [n_cal][T+1], got {tuple(dR.shape)} and {tuple(dw.shape)}")
     T = dR.shape[1] - 1
     if buffers is None:
-        buffers = TransitionBuffers(batch, T)
+        buffers = TransitionBuffers(batch, T, marginals=marginals)
     elif buffers.T != T:
         raise ValueError(f"buffers hold T={buffers.T}, the price paths T={T}")
+    if marginals and buffers.marg is None:
+        buffers.marg = torch.empty((T + 1, n_cal, n_a), dtype=F64, device=dev)
     m_term = _tables(m_term, n_cal, S, n_a)
     c_term = _tables(c_term, n_cal, S, n_a)
     if not torch.is_tensor(mass0):
@@ -179,9 +194,25 @@ def household_block(batch, R, w, m_term, c_term, mass0, want_c=True, export_poli
     transition_backward(batch, dR, dw, m_term, c_term, buffers, export_policy=export_policy, stream=stream)
     buffers.mass.copy_(mass0.reshape(n_cal, S, n_a))
     Ks, C = transition_forward(batch, buffers.lo, buffers.wlo, buffers.mass, T, buffers.work, dR, dw, want_c=want_c,
-                               stream=stream)
+                               stream=stream, marg=buffers.marg if marginals else None)
     return BlockResult(Ks=Ks, C=C, lo=buffers.lo, wlo=buffers.wlo, m0=buffers.m0 if export_policy else None,
-                       c0=buffers.c0 if export_policy else None, mass_T=buffers.mass)
+                       c0=buffers.c0 if export_policy else None, mass_T=buffers.mass,
+                       marg=buffers.marg if marginals else None)
+
+
+def path_wealth_stats(batch, marg, percentiles=None):
+    """Wealth statistics of every period of a path: ``marg`` [T+1][n_cal][n_a] (device, from
+    ``household_block(marginals=True)``) on the grids of ``batch``.  Returns ``stats.WealthStats``
+    of shape [n_cal][T+1]: the stack goes to ``stats.histogram_stats`` as it lies (period-major,
+    distribution d on grid d % n_cal) and only the results are transposed, on the host."""
+    n_cal, n_a = len(batch.cals), batch.n_a
+    if marg.dim() != 3 or marg.shape[1] != n_cal or marg.shape[2] != n_a:
+        raise ValueError(f"marg must be [T+1][n_cal={n_cal}][n_a={n_a}], got {tuple(marg.shape)}")
+    ws = _stats.histogram_stats(marg, batch.d_a, percentiles, marginal=True)
+    flip = lambda x: np.ascontiguousarray(np.swapaxes(x, 0, 1))   # noqa: E731
+    return _stats.WealthStats(lorenz=flip(ws.lorenz), percentile_values=flip(ws.percentile_values),
+                              gini=flip(ws.gini), mean=flip(ws.mean), total=flip(ws.total),
+                              bottom_share=flip(ws.bottom_share), percentiles=ws.percentiles)
 
 
 @dataclass
@@ -193,10 +224,11 @@ class TransitionResult:
     iterations: np.ndarray   # [n_cal] block evaluations used
     residual: np.ndarray     # [n_cal] max_t |Ks_t - K_t| / K_0 of the last evaluation
     status: np.ndarray       # [n_cal] 0: converged; bit 1: stopped at max_iter
+    stats: _stats.WealthStats | None = None   # [n_cal][T+1] wealth statistics of the path (percentiles=)
 
 
 def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=None, m_term=None, c_term=None,
-                     method="damped", jacobian=None):
+                     method="damped", jacobian=None, percentiles=None):
     """Equilibrium capital path of every calibration of ``batch`` after the TFP path Z
     ([T+1] or [n_cal][T+1], Z[T] = 1), from the distribution mass0 (default: batch.mass, the
     steady state) to the terminal policy (default: batch.last_tables).
@@ -210,7 +242,12 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
     replaces the update by K[1:] -= H^-1 (Ks[1:] - K[1:]), H the capital map of the household
     Jacobian at the steady state of ``batch`` (``jacobian``: a HouseholdJacobian of this batch
     and T to reuse, else one is built at r* = alpha K*^(alpha - 1) - delta, K* = sum batch.mass a).
-    H is factorised once per calibration; ``damping`` is not used."""
+    H is factorised once per calibration; ``damping`` is not used.
+
+    ``percentiles`` (a list or array in (0, 1)): also ``TransitionResult.stats``, the
+    ``path_wealth_stats`` of the solved path at these percentiles -- one more forward sweep, with
+    marginals, from mass0 on the lotteries of the last evaluation (which solved every
+    calibration at its final prices, the frozen ones included)."""
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     T = int(T)
     if method not in ("damped", "newton"):
@@ -267,7 +304,14 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
         rn, wn = path_prices(K, Z, batch.alpha, batch.delta)
         r[active], w[active] = rn[active], wn[active]
     status = np.where(active, 1, 0).astype(np.int32)
-    return TransitionResult(K=K, r=r, w=w, C=C, iterations=iterations, residual=residual, status=status)
+    path_stats = None
+    if percentiles is not None:
+        buffers.mass.copy_(mass0)
+        marg = torch.empty((T + 1, n_cal, n_a), dtype=F64, device=batch.device)
+        transition_forward(batch, buffers.lo, buffers.wlo, buffers.mass, T, buffers.work, want_c=False, marg=marg)
+        path_stats = path_wealth_stats(batch, marg, percentiles)
+    return TransitionResult(K=K, r=r, w=w, C=C, iterations=iterations, residual=residual, status=status,
+                            stats=path_stats)
 
 
 # -------------------------------------------------------------------------------------

@@ -571,6 +571,19 @@ int32_t aiy_transition_forward(aiy_handle* h, int32_t n_cal, int32_t S, int32_t 
                                const double* R, const double* w, const double* lab, void* work, double* mass,
                                double* Ks_out, double* C_out, aiy_stream stream);
 
+/* aiy_transition_forward, which also keeps the marginal over assets of every period's mass:
+ *   marg_out DEVICE [T+1][n_cal][n_a] (caller-owned): marg_out[t][cal][j] = sum over s, in
+ *            ascending s, of mass_t[cal][s][j], t = 0 .. T -- one more launch per period, on the
+ *            buffer that period's step just wrote (S times smaller than keeping the masses).
+ * mass, Ks_out and C_out have the bits aiy_transition_forward gives; the row check, the
+ * argument checks and the blocking are its own, and a failed row check leaves marg_out
+ * untouched too.  `work` is aiy_transition_work_bytes', unchanged. */
+int32_t aiy_transition_forward_marginals(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
+                                         const int32_t* lo, const double* wlo, const double* P,
+                                         const double* a_grid, const double* R, const double* w, const double* lab,
+                                         void* work, double* mass, double* Ks_out, double* C_out, double* marg_out,
+                                         aiy_stream stream);
+
 /* ------- sequence-space Jacobian of the household block (build-defined) ------- */
 
 /* The device stages of the fake-news algorithm at a steady state; the backward sweeps are
@@ -629,6 +642,39 @@ int32_t aiy_jacobian_contract(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n
 int32_t aiy_wealth_stats(aiy_handle* h, const double* data, const double* weights, int64_t n,
                          const double* pctiles, int32_t n_p, double* lorenz_out, double* pctl_out,
                          aiy_stream stream);
+
+/* ------- wealth statistics of histogram distributions (build-defined) ------- */
+
+/* Statistics of distributions over the ascending asset grid (no sort): for the marginal g[n_a]
+ * of one distribution, cw = cumsum(g), cd = cumsum(a g), F = cw / cw[-1], L = cd / cd[-1];
+ * Lorenz shares np.interp(p, F, L) and percentiles interp1d(F, a, bounds_error=False)(p) (HARK
+ * 0.12 get_lorenz_shares / get_percentiles with weights = g, presorted; NaN for p < F[0]), and
+ * gini = 1 - sum_j (F[j] - F[j-1]) (L[j] + L[j-1]), F[-1] = L[-1] = 0. */
+
+/* Device scratch of aiy_dist_stats for n_dist distributions of n_a nodes (cw and cd of every
+ * distribution, then the results), -1 for n_dist < 1 or n_a < 2.  Host-only. */
+int64_t aiy_dist_stats_work_bytes(int32_t n_dist, int32_t n_a);
+
+/* g[d][j] = sum over s, in ascending s, of mass[d][s][j]: the marginals of a stack.
+ *   mass: DEVICE [n_dist][S][n_a]; g: DEVICE [n_dist][n_a].  No atomics.  Asynchronous. */
+int32_t aiy_dist_marginal(aiy_handle* h, int32_t n_dist, int32_t S, int32_t n_a, const double* mass, double* g,
+                          aiy_stream stream);
+
+/* The statistics of a stack of marginals in one launch, one workgroup per distribution; every
+ * sum order depends on n_a only, so a distribution has the same bits alone and in any stack.
+ *   g           DEVICE [n_dist][n_a]
+ *   a_grid      DEVICE [n_grid][n_a]; distribution d uses grid d % n_grid (a [T+1][n_cal] stack
+ *               addresses its calibration's grid with n_grid = n_cal)
+ *   pctiles     HOST [n_p], in (0, 1), n_p <= 256; may be NULL with n_p = 0
+ *   work        DEVICE, aiy_dist_stats_work_bytes(n_dist, n_a)
+ *   lorenz_out / pctl_out  HOST [n_dist][n_p] (either may be NULL)
+ *   summary_out HOST [n_dist][4]: total = cw[-1], mean = cd[-1] / cw[-1], gini,
+ *               bottom_share = g[0] / cw[-1] (may be NULL)
+ * AIY_ERR_ARG for a percentile outside (0, 1), AIY_ERR_UNSUPPORTED for n_p > 256, both before
+ * any device work.  BLOCKING (synchronises `stream`). */
+int32_t aiy_dist_stats(aiy_handle* h, int32_t n_dist, int32_t n_grid, int32_t n_a, const double* g,
+                       const double* a_grid, const double* pctiles, int32_t n_p, void* work, double* lorenz_out,
+                       double* pctl_out, double* summary_out, aiy_stream stream);
 
 #ifdef __cplusplus
 }
