@@ -13,7 +13,8 @@ bisection on r, Young-lottery histogram, Rouwenhorst) in
 of the household block (``household_jacobian``, ``impulse_response``) in
 :mod:`aiyagari_hark_amd.transition`; wealth statistics of the panel and of histogram
 distributions and paths (``histogram_stats``, ``batch_wealth_stats``, ``path_wealth_stats``) in
-:mod:`aiyagari_hark_amd.stats`.
+:mod:`aiyagari_hark_amd.stats`; values on the histogram and consumption-equivalent welfare gains
+(``stationary_value``, ``path_value``, ``welfare.welfare``) in :mod:`aiyagari_hark_amd.welfare`.
 """
 from __future__ import annotations
 
@@ -33,4 +34,9 @@ def __getattr__(name):
     if name in ("histogram_stats", "batch_wealth_stats", "WealthStats"):
         from . import stats
         return getattr(stats, name)
+    if name in ("welfare", "stationary_value", "path_value", "consumption_equivalent", "WelfareResult"):
+        # ``welfare`` is the module (the import binds the name): its function is ``welfare.welfare``
+        import importlib
+        welfare = importlib.import_module(__name__ + ".welfare")
+        return welfare if name == "welfare" else getattr(welfare, name)
     raise AttributeError(name)

@@ -183,6 +183,14 @@ SIGNATURES = {
     "aiy_dist_marginal": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
     "aiy_dist_stats": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, c_double_p,
                                         ctypes.c_int32, vp, c_double_p, c_double_p, c_double_p, vp]),
+    "aiy_value_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "aiy_value_backward": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                            vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "aiy_value_stationary": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp,
+                                              vp, vp, vp, vp, c_double_p, ctypes.c_double, ctypes.c_int32,
+                                              ctypes.c_int32, vp, vp, c_int32_p, c_double_p, vp]),
+    "aiy_value_reduce": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, c_double_p, vp]),
+    "aiy_consumption_equivalent": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -79,6 +79,9 @@ struct aiy_handle {
   // wealth statistics (stats.hip): sort / scan scratch
   void* d_stats = nullptr;
   size_t stats_cap = 0;
+  // welfare (welfare.hip): the [n_cal][S] sums of aiy_value_reduce
+  double* d_welf = nullptr;
+  size_t welf_cap = 0;               // doubles
   unsigned long long* h_hdist = nullptr;
   double* h_K = nullptr;
   int* h_hlast = nullptr;

@@ -225,10 +225,11 @@ class TransitionResult:
     residual: np.ndarray     # [n_cal] max_t |Ks_t - K_t| / K_0 of the last evaluation
     status: np.ndarray       # [n_cal] 0: converged; bit 1: stopped at max_iter
     stats: _stats.WealthStats | None = None   # [n_cal][T+1] wealth statistics of the path (percentiles=)
+    welfare: object | None = None             # welfare.WelfareResult of the path against the steady state (welfare=True)
 
 
 def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=None, m_term=None, c_term=None,
-                     method="damped", jacobian=None, percentiles=None):
+                     method="damped", jacobian=None, percentiles=None, welfare=False):
     """Equilibrium capital path of every calibration of ``batch`` after the TFP path Z
     ([T+1] or [n_cal][T+1], Z[T] = 1), from the distribution mass0 (default: batch.mass, the
     steady state) to the terminal policy (default: batch.last_tables).
@@ -247,7 +248,13 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
     ``percentiles`` (a list or array in (0, 1)): also ``TransitionResult.stats``, the
     ``path_wealth_stats`` of the solved path at these percentiles -- one more forward sweep, with
     marginals, from mass0 on the lotteries of the last evaluation (which solved every
-    calibration at its final prices, the frozen ones included)."""
+    calibration at its final prices, the frozen ones included).
+
+    ``welfare=True``: also ``TransitionResult.welfare``, the ``welfare.WelfareResult`` of living
+    through the solved path from mass0 against staying at the steady state of ``batch``
+    (DESIGN.md §4m): V_base = ``welfare.stationary_value(batch)``, V = ``welfare.path_value`` on
+    the lotteries and prices of the last evaluation with V_base as the value from period T on.
+    Nothing else of the result changes."""
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     T = int(T)
     if method not in ("damped", "newton"):
@@ -310,8 +317,14 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
         marg = torch.empty((T + 1, n_cal, n_a), dtype=F64, device=batch.device)
         transition_forward(batch, buffers.lo, buffers.wlo, buffers.mass, T, buffers.work, want_c=False, marg=marg)
         path_stats = path_wealth_stats(batch, marg, percentiles)
+    gains = None
+    if welfare:
+        from . import welfare as _welfare
+        V_base = _welfare.stationary_value(batch)
+        V = _welfare.path_value(batch, buffers.lo, buffers.wlo, 1.0 + r, w, V_base)
+        gains = _welfare.welfare(batch, V, V_base, mass0)
     return TransitionResult(K=K, r=r, w=w, C=C, iterations=iterations, residual=residual, status=status,
-                            stats=path_stats)
+                            stats=path_stats, welfare=gains)
 
 
 # -------------------------------------------------------------------------------------

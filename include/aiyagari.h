@@ -676,6 +676,70 @@ int32_t aiy_dist_stats(aiy_handle* h, int32_t n_dist, int32_t n_grid, int32_t n_
                        const double* a_grid, const double* pctiles, int32_t n_p, void* work, double* lorenz_out,
                        double* pctl_out, double* summary_out, aiy_stream stream);
 
+/* ---- welfare: values on the histogram and consumption equivalents (build-defined) ---- */
+
+/* The exact expected discounted utility of the discretised economy.  The histogram is a Markov
+ * chain on (s, a_j): a household at node (s, j) of period t consumes
+ *   c_t[s][j] = R_t a_j + w_t lab_s - (wlo a[lo] + (1 - wlo) a[lo + 1])
+ * (the term aiy_transition_forward sums into C_out), moves to lo / lo + 1 with weights
+ * wlo / 1 - wlo and draws s' from P[s, .], so
+ *   V_t[s][j]     = u(c_t[s][j]) + beta (wlo G_{t+1}[s][lo] + (1 - wlo) G_{t+1}[s][lo + 1])
+ *   G_{t+1}[s][d] = sum over s', ascending, of P[s, s'] V_{t+1}[s'][d]
+ *   u(c) = log c for CRRA = 1, c^(1 - CRRA) / (1 - CRRA) otherwise (HARK's CRRAutility, no -1).
+ * The recursion is the transpose of the forward lottery step, hence, to rounding,
+ *   sum mass_0 V_0 = sum_{t<T} beta^t sum mass_t u(c_t) + beta^T sum mass_T V_T.
+ * c = 0 gives u = -inf and c < 0 gives NaN: a non-finite V, never a fault or a device-side error.
+ * The sum order of G depends on S only and nothing else is summed: a calibration has the same
+ * bits alone and in any batch.  lab, beta, crra: device, as in aiy_transition_model. */
+
+/* Device scratch of the two value calls below: two [n_cal][S][n_a] buffers for G and the
+ * convergence slots; -1 for n_a < 2 or S outside 1..AIY_MAX_STATES.  Host-only. */
+int64_t aiy_value_work_bytes(int32_t n_cal, int32_t S, int32_t n_a);
+
+/* V_t for t = T-1 .. 0 from V_term = V_T on the lotteries and prices of a path: one launch mixes
+ * V_term into G, then one fused launch per period (u(c), the gather from G_{t+1}, V_t, and G_t
+ * mixed by P through LDS), enqueued back to back.
+ *   lo / wlo   [T][n_cal][S][n_a]; R / w [n_cal][T+1]; V_term [n_cal][S][n_a]
+ *   V0_out     [n_cal][S][n_a]: V_0
+ *   V_path_out [T][n_cal][S][n_a] or NULL: every V_t (V_path_out[0] has the bits of V0_out)
+ * Null pointers and T < 1 give AIY_ERR_ARG before any launch.  A lottery index outside
+ * [0, n_a - 2] is read as the nearest one inside.  Asynchronous. */
+int32_t aiy_value_backward(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T, const int32_t* lo,
+                           const double* wlo, const double* P, const double* a_grid, const double* R,
+                           const double* w, const double* lab, const double* beta, const double* crra,
+                           const double* V_term, void* work, double* V0_out, double* V_path_out,
+                           aiy_stream stream);
+
+/* The steady value V = u(c) + beta Lambda V of the one lottery (lo, wlo) [n_cal][S][n_a] at the
+ * prices R, w [n_cal]: the same step iterated from the V given.  A calibration stops once
+ *   max |V_new - V| <= tol (1 - beta) / beta max |V_new|,
+ * which bounds |V - V*| by tol max |V| (contraction of modulus beta); both maxima come out of the
+ * step's launch into per-calibration slots, polled every `chunk` steps (chunk <= 0: 32), and a
+ * calibration that has stopped is skipped on device.  tol < 1e-13 is refused (AIY_ERR_ARG):
+ * rounding alone moves V by more per step.
+ *   beta_host HOST [n_cal]: the values of beta; V [n_cal][S][n_a] in: the start, out: the value
+ *   iters_out / dist_out HOST [n_cal]: steps run and the last max |V_new - V|; a calibration
+ *   still running at max_iter has iters_out == max_iter (nothing is raised).  BLOCKING. */
+int32_t aiy_value_stationary(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, const int32_t* lo,
+                             const double* wlo, const double* P, const double* a_grid, const double* R,
+                             const double* w, const double* lab, const double* beta, const double* crra,
+                             const double* beta_host, double tol, int32_t max_iter, int32_t chunk, double* V,
+                             void* work, int32_t* iters_out, double* dist_out, aiy_stream stream);
+
+/* W_out[c][s] = sum_j mass[c][s][j] V[c][s][j] (HOST [n_cal][S]; mass, V device): one workgroup
+ * per row, in aiy_dist_stats' order -- contiguous chunks of ceil(n_a / 256) nodes summed
+ * sequentially, then lanes and waves in a fixed order that depends on n_a only.  BLOCKING. */
+int32_t aiy_value_reduce(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, const double* mass,
+                         const double* V, double* W_out, aiy_stream stream);
+
+/* Consumption equivalent of every node, g_out[i] for i < n_cal * per (calibration i / per):
+ *   g = (V_new / V_base)^(1 / (1 - CRRA)) - 1 for CRRA != 1, exp((1 - beta)(V_new - V_base)) - 1
+ * for CRRA = 1: the uniform proportional change of consumption in every period and state that
+ * takes a household from V_base to V_new.  Elementwise.  Asynchronous. */
+int32_t aiy_consumption_equivalent(aiy_handle* h, int32_t n_cal, int64_t per, const double* V_new,
+                                   const double* V_base, const double* beta, const double* crra, double* g_out,
+                                   aiy_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
