@@ -304,6 +304,15 @@ def ptr(t) -> int | None:
     return t.data_ptr()
 
 
+def work_space(device, what: str, label: str, **sizes):
+    """The caller-owned work space of aiy_<what>_work_bytes(*sizes) as a uint8 tensor on ``device``;
+    ValueError (``label`` and the sizes) when the library does not support them (-1)."""
+    nbytes = int(getattr(handle(device.index).lib, f"aiy_{what}_work_bytes")(*(int(v) for v in sizes.values())))
+    if nbytes < 0:
+        raise ValueError(f"{label} sizes not supported: ".lstrip() + " ".join(f"{k}={v}" for k, v in sizes.items()))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def stream_ptr(stream=None) -> int:
     s = stream if stream is not None else torch.cuda.current_stream()
     return s.cuda_stream

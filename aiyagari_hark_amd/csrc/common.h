@@ -89,6 +89,17 @@ __device__ __forceinline__ int lower_bound(const double* __restrict__ x, int lo,
   }
   return lo;
 }
+// Upper bound (searchsorted side='right'): first index with x[idx] > q, or hi.
+__device__ __forceinline__ int upper_bound(const double* __restrict__ x, int lo, int hi, double q) {
+  while (lo < hi) {
+    int mid = lo + ((hi - lo) >> 1);
+    if (x[mid] <= q) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// Byte counts of caller-owned work spaces: every region starts on a 256-byte boundary.
+__host__ __device__ inline long long tab_align(long long b) { return (b + 255) / 256 * 256; }
 
 // HARK 0.12 LinearInterp._evaluate for one query given the bracket index
 // i = max(searchsorted(x[:-1], q), 1):

@@ -9,15 +9,14 @@
 //   gini          = 1 - sum_j (F[j] - F[j-1]) (L[j] + L[j-1]),  F[-1] = L[-1] = 0.
 //
 //   dist_stats_kernel   one workgroup of 256 threads per distribution, one launch per stack.
-//                       Thread k owns the contiguous chunk of ceil(n_a / 256) nodes from
-//                       k * chunk (threads past the end own nothing).  Pass 1: the chunk's sums
+//                       Thread k owns its row_chunk (transition_common.h).  Pass 1: the chunk's sums
 //                       of g and a g, sequentially.  The 256 chunk totals get an exclusive scan
 //                       in a fixed order: an inclusive shuffle scan per wave, then the waves in
 //                       ascending order through LDS.  Pass 2: cw[j] / cd[j] = the chunk's base +
 //                       its running sequential sum, written to the work space [n_dist][2][n_a],
 //                       and the thread's Gini terms (a chunk's first term takes the previous
 //                       chunk's last cw, cd = that chunk's base + total); the Gini partials are
-//                       summed by wave_sum_lane63, waves ascending.  After a block barrier
+//                       summed by row_block_sum (as value_reduce_kernel's).  After its barrier
 //                       threads 0 .. n_p - 1 do the two searches of stats_interp_kernel
 //                       (stats.hip) on cw, cd with sorted = a_grid, reading only the bracketing
 //                       entries; thread 0 writes the summary.
@@ -32,8 +31,8 @@
 
 namespace aiy {
 
-constexpr int kDsBlock = 256;
-constexpr int kDsWaves = kDsBlock / kWave;
+constexpr int kDsBlock = kTrBlock;
+constexpr int kDsWaves = kTrWaves;
 constexpr int kDsMaxPct = 256;
 constexpr int kDsSummary = 4;   // total, mean, gini, bottom_share
 
@@ -85,10 +84,8 @@ __global__ __launch_bounds__(kDsBlock) void dist_stats_kernel(DsArgs A) {
   __shared__ double s_lw[kDsBlock];        // last cw of every chunk
   __shared__ double s_ld[kDsBlock];        // last cd
 
-  const int chunk = (n + kDsBlock - 1) / kDsBlock;
-  const long long c0 = (long long)k * chunk;
-  const int j0 = c0 < n ? (int)c0 : n;
-  const int j1 = c0 + chunk < n ? (int)(c0 + chunk) : n;
+  int j0, j1;
+  const int chunk = row_chunk(n, k, j0, j1);
 
   double tw = 0.0, td = 0.0;   // pass 1: the chunk's totals
   for (int j = j0; j < j1; ++j) {
@@ -136,9 +133,7 @@ __global__ __launch_bounds__(kDsBlock) void dist_stats_kernel(DsArgs A) {
     Fp = F;
     Lp = L;
   }
-  const double gs = wave_sum_lane63(gacc);
-  if (lane == kWave - 1) s_wave[2][wid] = gs;
-  __syncthreads();   // also: the block's cw, cd are written
+  const double area = row_block_sum(gacc, s_wave[2]);   // its barrier: the block's cw, cd are written
 
   if (k < A.n_p) {
     const double p = A.pct[k];
@@ -184,8 +179,6 @@ __global__ __launch_bounds__(kDsBlock) void dist_stats_kernel(DsArgs A) {
     }
   }
   if (k == 0) {
-    double area = 0.0;
-    for (int q = 0; q < kDsWaves; ++q) area += s_wave[2][q];
     double* out = A.summary + dist * kDsSummary;
     out[0] = totw;
     out[1] = totd / totw;
@@ -201,12 +194,11 @@ struct DsLayout {
 };
 static bool ds_sizes_ok(int n_dist, int n_a) { return n_dist >= 1 && n_a >= 2; }
 static DsLayout ds_layout(int n_dist, int n_a) {
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   DsLayout L;
   size_t o = 0;
-  L.cum = o; o += up((size_t)n_dist * 2 * n_a * sizeof(double));
-  L.pct = o; o += up(kDsMaxPct * sizeof(double));
-  L.res = o; o += up((size_t)n_dist * (2 * kDsMaxPct + kDsSummary) * sizeof(double));
+  L.cum = o; o += tab_align((size_t)n_dist * 2 * n_a * sizeof(double));
+  L.pct = o; o += tab_align(kDsMaxPct * sizeof(double));
+  L.res = o; o += tab_align((size_t)n_dist * (2 * kDsMaxPct + kDsSummary) * sizeof(double));
   L.total = o;
   return L;
 }

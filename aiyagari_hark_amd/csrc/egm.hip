@@ -423,7 +423,7 @@ __global__ __launch_bounds__(kEgmBlock, (SC > 0 || SMAX <= 16) ? AIY_EGM_WAVES_P
   AIY_EGM_STAMP(W, 2);
   // block-uniform power kind: one straight-line body per kind
   const double crra = s_par[0];
-  const int pk = crra == 1.0 ? 1 : (crra == 3.0 ? 3 : (crra == 5.0 ? 5 : 0));
+  const int pk = crra_kind(crra);
   double* X = s_win[wave];   // slices: X | Y | XB | YB
   double* Y = X + kWin;
 #if AIY_EGM_DIAG == 1

@@ -192,6 +192,7 @@ __device__ __forceinline__ double interp_row_global_agent(const double* __restri
 // the ocml f64 pow was ~40 % of a stationary 24-calibration cycle.
 //   marg_u:   c^-rho          (MargValueFuncCRRA, AS:1479-1482)
 //   inv_marg: E^(-1/rho)      (AS:1490)
+__host__ __device__ inline int crra_kind(double gam) { return gam == 1.0 ? 1 : (gam == 3.0 ? 3 : (gam == 5.0 ? 5 : 0)); }
 template <int PK>
 __device__ __forceinline__ double marg_u(double c, double gam) {
   if constexpr (PK == 1) return 1.0 / c;

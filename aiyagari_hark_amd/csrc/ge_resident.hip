@@ -810,7 +810,7 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
   cx.aah = g.aah + (size_t)cal * kGeAaHist * S * n_a;
   cx.err = g.err;
   unsigned nb = 0, ne = 0;   // plain barriers / reductions passed (hk_solve counts on)
-  const int pk = cx.gam == 1.0 ? 1 : (cx.gam == 3.0 ? 3 : (cx.gam == 5.0 ? 5 : 0));
+  const int pk = crra_kind(cx.gam);
 
   for (int q = tid; q < S * S; q += TH) ge_s_Pe[q] = g.P[(size_t)cal * S * S + q];
   for (int q = tid; q < kGeMaxTiles * SMAX; q += TH) ge_s_hint[q] = -1;

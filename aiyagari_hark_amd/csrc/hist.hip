@@ -22,14 +22,6 @@ namespace aiy {
 
 constexpr int kSlots = 4;  // per-calibration convergence words (3 distance slots + flag)
 
-__device__ __forceinline__ int upper_bound(const double* __restrict__ x, int lo, int hi, double q) {
-  while (lo < hi) {
-    int mid = lo + ((hi - lo) >> 1);
-    if (x[mid] <= q) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void hist_lottery_kernel(int S, int n_a, const double* __restrict__ m_tab,
                                                            const double* __restrict__ c_tab,
                                                            const double* __restrict__ a_grid,

@@ -43,8 +43,6 @@ struct PanelTabGeom {
 constexpr int kTabOctaves = 12;
 constexpr int kTabFirst = 2;   // first indexed node of z
 
-__host__ __device__ inline long long tab_align(long long b) { return (b + 255) / 256 * 256; }
-
 __host__ __device__ inline PanelTabGeom panel_tab_geom(int n_lab, int n_M, int n_a, bool unemployed = false) {
   PanelTabGeom g;
   g.n = n_a;

@@ -22,13 +22,9 @@
 //   tr_range_kernel      jb[t][cal][s][d] = first j with lo >= d for every period at once (as
 //                        hist_range_kernel) and the row check: non-decreasing, in [0, n_a - 2].
 //   tr_forward_kernel    block = (calibration, 64 destination columns), one column per lane,
-//                        the waves share the states: for its s a lane sums the wlo mass terms
-//                        of the sources with lo = d, then the (1 - wlo) mass terms of those
-//                        with lo = d - 1, both ascending in j (np.add.at's order in hist_step),
-//                        into LDS; then each s' is mixed over s in ascending s
-//                        (hist_mix_kernel's order).  A range longer than a wave is summed by
-//                        the whole wave (lane-strided partials, then wave_sum_lane63).  No
-//                        atomics on mass.  The block's partial of Ks[t + 1] and C[t] goes to
+//                        the waves share the states: tr_pull (transition_common.h) of every
+//                        (s, column) into LDS, then tr_mix_forward for each s'.  No atomics on
+//                        mass.  The block's partial of Ks[t + 1] and C[t] goes to
 //                        [period][calibration][block]; tr_sum_kernel adds the blocks in block
 //                        order after the sweep (two fixed-order levels).
 //
@@ -65,15 +61,6 @@ struct TrBack {
   int* lo;                     // [n_cal][S][n_a] lottery of period u, or null
   double* wlo;
 };
-
-// searchsorted(a_grid, a', 'right') as hist_lottery_kernel
-__device__ __forceinline__ int tr_upper_bound(const double* __restrict__ x, int lo, int hi, double q) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (x[mid] <= q) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 // Bound of a wave-uniform query q over the sorted x[lo, hi), searched by the whole wave: every
 // round the 64 lanes probe 64 evenly spaced nodes (one load each), so a 10 000-node row takes
@@ -180,7 +167,7 @@ __device__ __forceinline__ void tr_lottery(const double* __restrict__ ag, int n,
     g0 = X[d - base];
     g1 = X[d + 1 - base];
   } else {   // NaN savings or a window too small: hist_lottery_kernel's own search
-    d = tr_upper_bound(ag, 0, n, ap) - 1;
+    d = upper_bound(ag, 0, n, ap) - 1;
     d = d < 0 ? 0 : (d > n - 2 ? n - 2 : d);
     g0 = ag[d];
     g1 = ag[d + 1];
@@ -261,7 +248,7 @@ __global__ __launch_bounds__(kTrBlock) void tr_backward_kernel(TrBack A) {
   const double a = A.a_grid[(size_t)cal * A.n_a + ic];
   const double gam = A.crra[cal];
   const double beta = A.beta[cal];
-  const int pk = gam == 1.0 ? 1 : (gam == 3.0 ? 3 : (gam == 5.0 ? 5 : 0));   // block-uniform power kind
+  const int pk = crra_kind(gam);   // block-uniform power kind
   double* X = s_win[wave];
   double* Y = X + kWin;
   __syncthreads();
@@ -383,99 +370,46 @@ __global__ __launch_bounds__(kTrBlock) void tr_K0_kernel(TrFwd A, const double* 
 template <bool WITH_C>
 __global__ __launch_bounds__(kTrBlock) void tr_forward_kernel(TrFwd A, int t, const double* __restrict__ mass,
                                                               double* __restrict__ mass_out) {
-  const int cal = blockIdx.y, S = A.S, n_a = A.n_a;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int lane = threadIdx.x & (kWave - 1);
-  const int d = blockIdx.x * kTrCols + lane;
-  const bool active = d < n_a;
-  const size_t rows = (size_t)cal * S;
-  const size_t trow = ((size_t)t * A.n_cal + cal) * S;   // first row of (t, cal) in the [T][n_cal][S][.] arrays
-  const double* ag = A.a_grid + (size_t)cal * n_a;
-  const double ad = ag[active ? d : n_a - 1];
+  const int S = A.S, n_a = A.n_a;
+  const TrPlace p = tr_place(S, n_a);
+  const int d = p.col;
+  const size_t trow = ((size_t)t * A.n_cal + p.cal) * S;   // first row of (t, cal) in the [T][n_cal][S][.] arrays
+  const double* ag = A.a_grid + (size_t)p.cal * n_a;
+  const double ad = ag[p.active ? d : n_a - 1];
   double Rt = 0.0, wt = 0.0;
   if constexpr (WITH_C) {
-    Rt = A.R[(size_t)cal * (A.T + 1) + t];
-    wt = A.w[(size_t)cal * (A.T + 1) + t];
+    Rt = A.R[(size_t)p.cal * (A.T + 1) + t];
+    wt = A.w[(size_t)p.cal * (A.T + 1) + t];
   }
-  __shared__ double Tl[AIY_MAX_STATES * kTrCols];   // T_s[d] of the block's columns
+  __shared__ double Tl[kTrTile];   // T_s[d] of the block's columns
   double cacc = 0.0;
   // pull: wave w forms T_s of the block's columns for s = w, w + 4, ...
 #pragma unroll 1
-  for (int s = wave; s < S; s += kTrWaves) {
-    const int* J = A.jb + (trow + s) * (size_t)(n_a + 1);
-    const double* W = A.wlo + (trow + s) * (size_t)n_a;
-    const double* Q = mass + (rows + s) * (size_t)n_a;
-    int a0 = 0, a1 = 0, a2 = 0;   // lo = d - 1: [a0, a1), lo = d: [a1, a2)
-    if (active) {
-      a1 = J[d];
-      a2 = J[d + 1];
-      a0 = d > 0 ? J[d - 1] : a1;
-    }
+  for (int s = p.wave; s < S; s += kTrWaves) {
     double ls = 0.0;
-    if constexpr (WITH_C) ls = wt * A.lab[rows + s];
-    const bool heavy = (a2 - a1 > kWave) || (a1 - a0 > kWave);
-    double ts = 0.0;
-    if (!heavy) {
-      for (int j = a1; j < a2; ++j) {                      // np.add.at(T, lo, w q), ascending j
-        const double term = W[j] * Q[j];
-        ts += term;
-        if constexpr (WITH_C) cacc += term * ((Rt * ag[j] + ls) - ad);
-      }
-      for (int j = a0; j < a1; ++j) {                      // np.add.at(T, lo + 1, (1 - w) q)
-        const double term = (1.0 - W[j]) * Q[j];
-        ts += term;
-        if constexpr (WITH_C) cacc += term * ((Rt * ag[j] + ls) - ad);
-      }
-    }
-    unsigned long long hm = __ballot(heavy);
-    while (hm) {   // wave-uniform: the whole wave sums one lane's ranges
-      const int hl = __builtin_ctzll(hm);
-      hm &= hm - 1ull;
-      const int b0 = __builtin_amdgcn_readlane(a0, hl), b1 = __builtin_amdgcn_readlane(a1, hl),
-                b2 = __builtin_amdgcn_readlane(a2, hl);
-      const double adh = __shfl(ad, hl, kWave);
-      double pa = 0.0, pb = 0.0, pc = 0.0;
-      for (int j = b1 + lane; j < b2; j += kWave) {
-        const double term = W[j] * Q[j];
-        pa += term;
-        if constexpr (WITH_C) pc += term * ((Rt * ag[j] + ls) - adh);
-      }
-      for (int j = b0 + lane; j < b1; j += kWave) {
-        const double term = (1.0 - W[j]) * Q[j];
-        pb += term;
-        if constexpr (WITH_C) pc += term * ((Rt * ag[j] + ls) - adh);
-      }
-      const double ta = wave_sum_lane63(pa), tb = wave_sum_lane63(pb);
-      const double tot = __shfl(ta, kWave - 1, kWave) + __shfl(tb, kWave - 1, kWave);
-      double tc = 0.0;
-      if constexpr (WITH_C) tc = __shfl(wave_sum_lane63(pc), kWave - 1, kWave);
-      if (lane == hl) {
-        ts = tot;
-        cacc += tc;
-      }
-    }
-    Tl[s * kTrCols + lane] = ts;
+    if constexpr (WITH_C) ls = wt * A.lab[p.rows + s];
+    Tl[s * kTrCols + p.lane] =
+        tr_pull<WITH_C>(A.jb + (trow + s) * (size_t)(n_a + 1), A.wlo + (trow + s) * (size_t)n_a,
+                        mass + (p.rows + s) * (size_t)n_a, d, p.active, p.lane, ag, Rt, ls, ad, cacc);
   }
   __syncthreads();
-  // mix: wave w forms mass'[s'] = sum_s P[s, s'] T_s in ascending s (hist_mix_kernel's order)
-  // for s' = w, w + 4, ...; P[s, s'] is wave-uniform
-  const double* Pc = A.P + rows * S;
+  // mix: wave w forms mass'[s'] for s' = w, w + 4, ...
+  const double* Pc = A.P + p.rows * S;
   double kacc = 0.0;
 #pragma unroll 1
-  for (int sp = wave; sp < S; sp += kTrWaves) {
-    double acc = 0.0;
-    for (int s = 0; s < S; ++s) acc += Pc[(size_t)s * S + sp] * Tl[s * kTrCols + lane];
-    if (active) {
-      mass_out[(rows + sp) * (size_t)n_a + d] = acc;
+  for (int sp = p.wave; sp < S; sp += kTrWaves) {
+    const double acc = tr_mix_forward(Pc, Tl, S, sp, p.lane);
+    if (p.active) {
+      mass_out[(p.rows + sp) * (size_t)n_a + d] = acc;
       kacc += acc * ad;
     }
   }
   __shared__ double red[kTrWaves];
   const double k = tr_block_sum(kacc, red);
-  if (threadIdx.x == 0) A.Kpart[((size_t)(t + 1) * A.n_cal + cal) * A.nblk + blockIdx.x] = k;
+  if (threadIdx.x == 0) A.Kpart[((size_t)(t + 1) * A.n_cal + p.cal) * A.nblk + blockIdx.x] = k;
   if constexpr (WITH_C) {
     const double c = tr_block_sum(cacc, red);
-    if (threadIdx.x == 0) A.Cpart[((size_t)t * A.n_cal + cal) * A.nblk + blockIdx.x] = c;
+    if (threadIdx.x == 0) A.Cpart[((size_t)t * A.n_cal + p.cal) * A.nblk + blockIdx.x] = c;
   }
 }
 
@@ -542,29 +476,20 @@ static bool tr_sizes_ok(int n_cal, int S, int n_a, int T) {
 }
 
 static TrLayout tr_layout(int n_cal, int S, int n_a, int T) {
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   TrLayout L;
-  L.nblk = (n_a + kTrCols - 1) / kTrCols;
+  L.nblk = tr_nblk(n_a);
   L.tab_doubles = (size_t)n_cal * S * (n_a + 1);
   size_t o = 0;
-  L.tab = o;   o += up(4 * L.tab_doubles * sizeof(double));                      // (m, c) x ping-pong
-  L.jb = o;    o += up((size_t)T * n_cal * S * (n_a + 1) * sizeof(int));
-  L.alt = o;   o += up((size_t)n_cal * S * n_a * sizeof(double));               // ping-pong partner of mass
-  L.kpart = o; o += up((size_t)(T + 1) * n_cal * L.nblk * sizeof(double));
-  L.cpart = o; o += up((size_t)T * n_cal * L.nblk * sizeof(double));
-  L.ks = o;    o += up((size_t)n_cal * (T + 1) * sizeof(double));
-  L.c = o;     o += up((size_t)n_cal * T * sizeof(double));
+  L.tab = o;   o += tab_align(4 * L.tab_doubles * sizeof(double));                      // (m, c) x ping-pong
+  L.jb = o;    o += tab_align((size_t)T * n_cal * S * (n_a + 1) * sizeof(int));
+  L.alt = o;   o += tab_align((size_t)n_cal * S * n_a * sizeof(double));               // ping-pong partner of mass
+  L.kpart = o; o += tab_align((size_t)(T + 1) * n_cal * L.nblk * sizeof(double));
+  L.cpart = o; o += tab_align((size_t)T * n_cal * L.nblk * sizeof(double));
+  L.ks = o;    o += tab_align((size_t)n_cal * (T + 1) * sizeof(double));
+  L.c = o;     o += tab_align((size_t)n_cal * T * sizeof(double));
   L.flag = o;  o += 256;
   L.total = o;
   return L;
-}
-
-static int32_t tr_check(aiy_handle* h, int n_cal, int S, int n_a, int T) {
-  if (T < 1) return fail(h, AIY_ERR_ARG, "T=%d must be >= 1", T);
-  if (n_a < 2) return fail(h, AIY_ERR_ARG, "n_a=%d must be >= 2", n_a);
-  if (S < 1 || S > AIY_MAX_STATES) return fail(h, AIY_ERR_ARG, "S=%d outside 1..%d", S, AIY_MAX_STATES);
-  if (!tr_sizes_ok(n_cal, S, n_a, T)) return fail(h, AIY_ERR_ARG, "bad sizes n_cal=%d S=%d n_a=%d T=%d", n_cal, S, n_a, T);
-  return AIY_OK;
 }
 
 }  // namespace aiy
@@ -581,7 +506,7 @@ extern "C" int32_t aiy_transition_backward(aiy_handle* h, const aiy_transition_m
   if (!h) return AIY_ERR_ARG;
   if (!M) return fail(h, AIY_ERR_ARG, "null model");
   const int n_cal = M->n_cal, S = M->S, n_a = M->n_a, T = M->T;
-  int32_t rc = tr_check(h, n_cal, S, n_a, T);
+  int32_t rc = tr_check(h, n_cal, S, n_a, true, T);
   if (rc) return rc;
   if (!M->a_grid || !M->P || !M->lab || !M->beta || !M->crra || !M->R || !M->w || !M->m_term || !M->c_term)
     return fail(h, AIY_ERR_ARG, "null model array");
@@ -629,7 +554,7 @@ static int32_t tr_forward_sweep(aiy_handle* h, int32_t n_cal, int32_t S, int32_t
                                 const double* w, const double* lab, void* work, double* mass, double* Ks_out,
                                 double* C_out, double* marg, aiy_stream stream) {
   if (!h) return AIY_ERR_ARG;
-  int32_t rc = tr_check(h, n_cal, S, n_a, T);
+  int32_t rc = tr_check(h, n_cal, S, n_a, true, T);
   if (rc) return rc;
   if (!lo || !wlo || !P || !a_grid || !work || !mass || !Ks_out) return fail(h, AIY_ERR_ARG, "null buffer");
   if (C_out && (!R || !w || !lab)) return fail(h, AIY_ERR_ARG, "C_out needs R, w and lab");

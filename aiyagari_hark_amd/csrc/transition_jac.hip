@@ -3,17 +3,18 @@
 // 2021).  The backward sweeps are aiy_transition_backward's; this file adds
 //
 //   jac_fanout_kernel    out[t] = lottery step of ONE mass with (lo[t], wlo[t]) for every
-//                        period t of a [T'][n_cal][S][n_a] lottery: tr_forward_kernel's pull
-//                        and mix (same ranges, same summation order, so the same bits as
-//                        aiy_transition_forward with T = 1 on that period), the period in
-//                        blockIdx.z -- the periods do not depend on each other.
+//                        period t of a [T'][n_cal][S][n_a] lottery: the tr_pull and
+//                        tr_mix_forward (transition_common.h) that tr_forward_kernel calls, so
+//                        the same bits as aiy_transition_forward with T = 1 on that period, the
+//                        period in blockIdx.z -- the periods do not depend on each other.
 //   jac_diff_kernel      shocked <- (shocked - ghost) / h, element by element, before anything
 //                        is summed.
 //   jac_expect_kernel    E_{k+1}[s][j] = wlo G_k[s][lo] + (1 - wlo) G_k[s][lo + 1] with
-//                        G_k[s][d] = sum_{s'} P[s, s'] E_k[s'][d] in ascending s': a block owns
-//                        (calibration, 64 columns, all states), gathers from the previous
-//                        launch's G, writes E_{k+1}, and mixes its own columns from LDS into
-//                        G_{k+1} (ping-pong), so no separate mix launch and no atomics.
+//                        G_k[s][d] = sum_{s'} P[s, s'] E_k[s'][d] in ascending s': the adjoint
+//                        step of transition_common.h (tr_adjoint_values, tr_adjoint_mix).  A
+//                        block owns (calibration, 64 columns, all states), gathers from the
+//                        previous launch's G, writes E_{k+1}, and mixes its own columns from LDS
+//                        into G_{k+1} (ping-pong), so no separate mix launch and no atomics.
 //   jac_contract_kernel  partial[cal][chunk][t][col] = sum over one chunk of the long index of
 //                        E[t][cal][.] dD[col][cal][.], both inputs' columns in one pass over E,
 //                        on v_mfma_f64_16x16x4_f64: a block owns a 64 x 64 tile of one chunk,
@@ -45,55 +46,22 @@ struct JacFan {
 
 __global__ __launch_bounds__(kTrBlock) void jac_fanout_kernel(JacFan A, const double* __restrict__ mass,
                                                               double* __restrict__ out) {
-  const int cal = blockIdx.y, t = blockIdx.z, S = A.S, n_a = A.n_a;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int lane = threadIdx.x & (kWave - 1);
-  const int d = blockIdx.x * kTrCols + lane;
-  const bool active = d < n_a;
-  const size_t rows = (size_t)cal * S;
-  const size_t trow = ((size_t)t * A.n_cal + cal) * S;   // first row of (t, cal) in the [T'][n_cal][S][.] arrays
-  __shared__ double Tl[AIY_MAX_STATES * kTrCols];   // T_s[d] of the block's columns
-  // pull: wave w forms T_s of the block's columns for s = w, w + 4, ... (tr_forward_kernel)
+  const int t = blockIdx.z, S = A.S, n_a = A.n_a;
+  const TrPlace p = tr_place(S, n_a);
+  const size_t trow = ((size_t)t * A.n_cal + p.cal) * S;   // first row of (t, cal) in the [T'][n_cal][S][.] arrays
+  __shared__ double Tl[kTrTile];   // T_s[d] of the block's columns
+  double none = 0.0;               // (no consumption term)
 #pragma unroll 1
-  for (int s = wave; s < S; s += kTrWaves) {
-    const int* J = A.jb + (trow + s) * (size_t)(n_a + 1);
-    const double* W = A.wlo + (trow + s) * (size_t)n_a;
-    const double* Q = mass + (rows + s) * (size_t)n_a;
-    int a0 = 0, a1 = 0, a2 = 0;   // lo = d - 1: [a0, a1), lo = d: [a1, a2)
-    if (active) {
-      a1 = J[d];
-      a2 = J[d + 1];
-      a0 = d > 0 ? J[d - 1] : a1;
-    }
-    const bool heavy = (a2 - a1 > kWave) || (a1 - a0 > kWave);
-    double ts = 0.0;
-    if (!heavy) {
-      for (int j = a1; j < a2; ++j) ts += W[j] * Q[j];           // np.add.at(T, lo, w q), ascending j
-      for (int j = a0; j < a1; ++j) ts += (1.0 - W[j]) * Q[j];   // np.add.at(T, lo + 1, (1 - w) q)
-    }
-    unsigned long long hm = __ballot(heavy);
-    while (hm) {   // wave-uniform: the whole wave sums one lane's ranges
-      const int hl = __builtin_ctzll(hm);
-      hm &= hm - 1ull;
-      const int b0 = __builtin_amdgcn_readlane(a0, hl), b1 = __builtin_amdgcn_readlane(a1, hl),
-                b2 = __builtin_amdgcn_readlane(a2, hl);
-      double pa = 0.0, pb = 0.0;
-      for (int j = b1 + lane; j < b2; j += kWave) pa += W[j] * Q[j];
-      for (int j = b0 + lane; j < b1; j += kWave) pb += (1.0 - W[j]) * Q[j];
-      const double ta = wave_sum_lane63(pa), tb = wave_sum_lane63(pb);
-      const double tot = __shfl(ta, kWave - 1, kWave) + __shfl(tb, kWave - 1, kWave);
-      if (lane == hl) ts = tot;
-    }
-    Tl[s * kTrCols + lane] = ts;
-  }
+  for (int s = p.wave; s < S; s += kTrWaves)
+    Tl[s * kTrCols + p.lane] =
+        tr_pull<false>(A.jb + (trow + s) * (size_t)(n_a + 1), A.wlo + (trow + s) * (size_t)n_a,
+                       mass + (p.rows + s) * (size_t)n_a, p.col, p.active, p.lane, nullptr, 0.0, 0.0, 0.0, none);
   __syncthreads();
-  // mix: out[s'] = sum_s P[s, s'] T_s in ascending s, for s' = w, w + 4, ...
-  const double* Pc = A.P + rows * S;
+  const double* Pc = A.P + p.rows * S;
 #pragma unroll 1
-  for (int sp = wave; sp < S; sp += kTrWaves) {
-    double acc = 0.0;
-    for (int s = 0; s < S; ++s) acc += Pc[(size_t)s * S + sp] * Tl[s * kTrCols + lane];
-    if (active) out[(trow + sp) * (size_t)n_a + d] = acc;
+  for (int sp = p.wave; sp < S; sp += kTrWaves) {
+    const double acc = tr_mix_forward(Pc, Tl, S, sp, p.lane);
+    if (p.active) out[(trow + sp) * (size_t)n_a + p.col] = acc;
   }
 }
 
@@ -115,43 +83,23 @@ struct JacExp {
   const double* a_grid;   // [n_cal][n_a]
 };
 
-// INIT: E_0 = a.  Else E_{k+1} from G_k.  Both write G of what they wrote to E.
+// INIT: E_0 = a.  Else E_{k+1} from G_k (the row check keeps lo in [0, n_a - 2]).  Both write G of
+// what they wrote to E.
 template <bool INIT>
 __global__ __launch_bounds__(kTrBlock) void jac_expect_kernel(JacExp A, const double* __restrict__ G_in,
                                                               double* __restrict__ E_out, double* __restrict__ G_out) {
-  const int cal = blockIdx.y, S = A.S, n_a = A.n_a;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int lane = threadIdx.x & (kWave - 1);
-  const int j = blockIdx.x * kTrCols + lane;
-  const bool active = j < n_a;
-  const size_t rows = (size_t)cal * S;
-  __shared__ double El[AIY_MAX_STATES * kTrCols];   // E_{k+1}[s'] of the block's columns
-#pragma unroll 1
-  for (int s = wave; s < S; s += kTrWaves) {
-    double e = 0.0;
-    if (active) {
-      const size_t o = (rows + s) * (size_t)n_a + j;
-      if constexpr (INIT) {
-        e = A.a_grid[(size_t)cal * n_a + j];
-      } else {
-        const double* g = G_in + (rows + s) * (size_t)n_a;
-        const int d = A.lo[o];
-        const double wl = A.wlo[o];
-        e = wl * g[d] + (1.0 - wl) * g[d + 1];
-      }
-      E_out[o] = e;
-    }
-    El[s * kTrCols + lane] = e;
-  }
+  const int S = A.S, n_a = A.n_a;
+  const TrPlace p = tr_place(S, n_a);
+  __shared__ double El[kTrTile];   // E_{k+1}[s'] of the block's columns
+  tr_adjoint_values(p, S, n_a, El, [&](int s, size_t o) {
+    double e;
+    if constexpr (INIT) e = A.a_grid[(size_t)p.cal * n_a + p.col];
+    else e = tr_gather(G_in + (p.rows + s) * (size_t)n_a, A.lo[o], A.wlo[o]);
+    E_out[o] = e;
+    return e;
+  });
   __syncthreads();
-  // G[s] = sum_{s'} P[s, s'] E[s'] in ascending s'; P[s, s'] is wave-uniform
-  const double* Pc = A.P + rows * S;
-#pragma unroll 1
-  for (int s = wave; s < S; s += kTrWaves) {
-    double acc = 0.0;
-    for (int sp = 0; sp < S; ++sp) acc += Pc[(size_t)s * S + sp] * El[sp * kTrCols + lane];
-    if (active) G_out[(rows + s) * (size_t)n_a + j] = acc;
-  }
+  tr_adjoint_mix(p, S, n_a, A.P, El, G_out);
 }
 
 // ---------------------------------------------------------------------------------
@@ -282,26 +230,22 @@ static bool jac_sizes_ok(int n_cal, int S, int n_a, int T) {
 }
 
 static JacLayout jac_layout(int n_cal, int S, int n_a, int T) {
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   JacLayout L;
   L.per = (size_t)n_cal * S * n_a;
   L.nchunk = (int)(((size_t)S * n_a + kJacChunk - 1) / kJacChunk);
-  L.nblk = (n_a + kTrCols - 1) / kTrCols;
+  L.nblk = tr_nblk(n_a);
   size_t o = 0;
-  L.jb = o;   o += up((size_t)(T + 1) * n_cal * S * (n_a + 1) * sizeof(int));               // fan-out: T + 1 periods
-  L.g = o;    o += up(2 * L.per * sizeof(double));                                           // G ping-pong
-  L.part = o; o += up((size_t)n_cal * L.nchunk * T * 2 * (T + 1) * sizeof(double));
+  L.jb = o;   o += tab_align((size_t)(T + 1) * n_cal * S * (n_a + 1) * sizeof(int));               // fan-out: T + 1 periods
+  L.g = o;    o += tab_align(2 * L.per * sizeof(double));                                           // G ping-pong
+  L.part = o; o += tab_align((size_t)n_cal * L.nchunk * T * 2 * (T + 1) * sizeof(double));
   L.flag = o; o += 256;
   L.total = o;
   return L;
 }
 
+// tr_check and the contraction's limits
 static int32_t jac_check(aiy_handle* h, int n_cal, int S, int n_a, int T) {
-  if (T < 1) return fail(h, AIY_ERR_ARG, "T=%d must be >= 1", T);
-  if (n_a < 2) return fail(h, AIY_ERR_ARG, "n_a=%d must be >= 2", n_a);
-  if (S < 1 || S > AIY_MAX_STATES) return fail(h, AIY_ERR_ARG, "S=%d outside 1..%d", S, AIY_MAX_STATES);
-  if (!jac_sizes_ok(n_cal, S, n_a, T)) return fail(h, AIY_ERR_ARG, "bad sizes n_cal=%d S=%d n_a=%d T=%d", n_cal, S, n_a, T);
-  return AIY_OK;
+  return tr_check(h, n_cal, S, n_a, true, T, jac_sizes_ok(n_cal, S, n_a, T));
 }
 
 }  // namespace aiy

@@ -9,26 +9,25 @@
 //   G_{t+1}[s][d] = sum over s', ascending, of P[s, s'] V_{t+1}[s'][d]
 //   u(c) = log c (CRRA = 1), c^(1 - CRRA) / (1 - CRRA) otherwise; c = 0 gives -inf, c < 0 NaN.
 //
-// This is the transpose of the forward lottery step (jac_expect_kernel's recursion with a
-// per-period lottery, a flow payoff and a discount), so sum mass_0 V_0 equals the discounted sum
-// of sum mass_t u(c_t) plus beta^T sum mass_T V_T to rounding.
+// This is the transpose of the forward lottery step (the adjoint step of transition_common.h, as
+// jac_expect_kernel, with a per-period lottery, a flow payoff and a discount), so sum mass_0 V_0
+// equals the discounted sum of sum mass_t u(c_t) plus beta^T sum mass_T V_T to rounding.
 //
-//   value_step_kernel   jac_expect_kernel's layout: a block owns (calibration, 64 columns, all
-//                       states); wave w forms V[s] for s = w, w + 4, ... from the previous
-//                       launch's G (a gather at lo, lo + 1), writes it, keeps it in LDS, and after
-//                       a barrier mixes the block's own columns by P into the other G buffer
-//                       (ping-pong): one launch per period, no separate mix launch, no atomics in
-//                       the recursion.  MIX only mixes a given V into G (the terminal value);
+//   value_step_kernel   tr_adjoint_values / tr_adjoint_mix (transition_common.h): a block owns
+//                       (calibration, 64 columns, all states); wave w forms V[s] for s = w, w + 4,
+//                       ... from the previous launch's G (tr_gather at lo, lo + 1), writes it, keeps
+//                       it in LDS, and after a barrier mixes the block's own columns by P into the
+//                       other G buffer (ping-pong): one launch per period, no separate mix launch,
+//                       no atomics in the recursion.  MIX only mixes a given V into G (the terminal value);
 //                       PATH is one period of a path; STEADY is one step of the value iteration
 //                       with the one lottery: it also folds max |V_new - V| and max |V_new| into
 //                       the calibration's slots (64-bit atomicMax on the bit pattern of a
 //                       non-negative double, as the EGM solve keeps its distances -- a maximum does
 //                       not depend on the order) and skips a calibration whose previous step met
 //                       max |V_new - V| <= tol (1 - beta) / beta max |V_new|.
-//   value_reduce_kernel W[cal][s] = sum_j mass V: dist_stats_kernel's conventions -- a workgroup
-//                       of 256 threads per row, thread k sums the contiguous chunk of
-//                       ceil(n_a / 256) nodes from k * chunk sequentially, the chunk totals are
-//                       added by wave_sum_lane63 and the waves in ascending order.
+//   value_reduce_kernel W[cal][s] = sum_j mass V: a workgroup of 256 threads per row, thread k
+//                       sums its row_chunk sequentially, the chunk totals are added by
+//                       row_block_sum (transition_common.h, shared with dist_stats_kernel).
 //   value_ce_kernel     the consumption equivalent of every node, element by element.
 //
 // Every sum order is a function of S (the mix) or n_a (the reduction) only: a calibration has the
@@ -36,6 +35,7 @@
 // that is not one (never produced by the library) cannot make the kernel read outside G.
 // Offsets are size_t throughout (24 x 300 x 7 x 10 000 > 2^31).
 #include "common.h"
+#include "egm_common.h"
 #include "hist_cluster.h"
 #include "internal.h"
 #include "transition_common.h"
@@ -49,8 +49,6 @@ constexpr int kValMix = 0, kValPath = 1, kValSteady = 2;
 // Convergence slots of one calibration (unsigned long long): max |V_new - V| and max |V_new| of
 // the steps k % 3 == 0, 1, 2, the sticky converged flag, the last step that ran.
 constexpr int kValDist = 0, kValMax = 3, kValFlag = 6, kValLast = 7, kValSlots = 8;
-constexpr int kVrBlock = 256;
-constexpr int kVrWaves = kVrBlock / kWave;
 
 struct ValArgs {
   int S, n_a, pstride;    // pstride: T + 1 on a path, 1 at the steady state
@@ -102,13 +100,10 @@ __global__ __launch_bounds__(kTrBlock) void value_step_kernel(ValArgs A, int t, 
                                                               const double* __restrict__ G_in, double* Va,
                                                               double* __restrict__ Vb, double* __restrict__ G_out,
                                                               int iter, unsigned long long* slots, double tol) {
-  const int cal = blockIdx.y, S = A.S, n_a = A.n_a;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int lane = threadIdx.x & (kWave - 1);
-  const int j = blockIdx.x * kTrCols + lane;
-  const bool active = j < n_a;
-  const size_t rows = (size_t)cal * S;
-  __shared__ double El[AIY_MAX_STATES * kTrCols];   // V[s'] of the block's columns
+  const int S = A.S, n_a = A.n_a;
+  const TrPlace p = tr_place(S, n_a);
+  const int cal = p.cal, wave = p.wave, lane = p.lane;
+  __shared__ double El[kTrTile];   // V[s'] of the block's columns
   __shared__ double red[2][kTrWaves];
   __shared__ int s_skip;
   double beta = 0.0;
@@ -140,35 +135,29 @@ __global__ __launch_bounds__(kTrBlock) void value_step_kernel(ValArgs A, int t, 
     Rt = A.R[(size_t)cal * A.pstride + t];
     wt = A.w[(size_t)cal * A.pstride + t];
     crra = A.crra[cal];
-    kind = crra == 1.0 ? 1 : (crra == 3.0 ? 3 : (crra == 5.0 ? 5 : 0));
-    aj = ag[active ? j : n_a - 1];
+    kind = crra_kind(crra);
+    aj = ag[p.active ? p.col : n_a - 1];
   }
   double dmax = 0.0, vmax = 0.0;
-#pragma unroll 1
-  for (int s = wave; s < S; s += kTrWaves) {
-    double v = 0.0;
-    if (active) {
-      const size_t o = (rows + s) * (size_t)n_a + j;
-      if constexpr (MODE == kValMix) {
-        v = V_src[o];
-      } else {
-        const double* g = G_in + (rows + s) * (size_t)n_a;
-        int d = A.lo[o];
-        d = d < 0 ? 0 : (d > n_a - 2 ? n_a - 2 : d);
-        const double wl = A.wlo[o];
-        const double c = (Rt * aj + wt * A.lab[rows + s]) - (wl * ag[d] + (1.0 - wl) * ag[d + 1]);
-        v = val_utility(c, kind, crra) + beta * (wl * g[d] + (1.0 - wl) * g[d + 1]);
-        if constexpr (MODE == kValSteady) {
-          dmax = nan_max(dmax, fabs(v - Va[o]));
-          vmax = nan_max(vmax, fabs(v));
-        }
-        if (Va != nullptr) Va[o] = v;
-        if constexpr (MODE == kValPath)
-          if (Vb != nullptr) Vb[o] = v;
+  tr_adjoint_values(p, S, n_a, El, [&](int s, size_t o) {
+    if constexpr (MODE == kValMix) {
+      return V_src[o];
+    } else {
+      int d = A.lo[o];
+      d = d < 0 ? 0 : (d > n_a - 2 ? n_a - 2 : d);
+      const double wl = A.wlo[o];
+      const double c = (Rt * aj + wt * A.lab[p.rows + s]) - tr_gather(ag, d, wl);
+      const double v = val_utility(c, kind, crra) + beta * tr_gather(G_in + (p.rows + s) * (size_t)n_a, d, wl);
+      if constexpr (MODE == kValSteady) {
+        dmax = nan_max(dmax, fabs(v - Va[o]));
+        vmax = nan_max(vmax, fabs(v));
       }
+      if (Va != nullptr) Va[o] = v;
+      if constexpr (MODE == kValPath)
+        if (Vb != nullptr) Vb[o] = v;
+      return v;
     }
-    El[s * kTrCols + lane] = v;
-  }
+  });
   if constexpr (MODE == kValSteady) {
     dmax = wave_nan_max(dmax);
     vmax = wave_nan_max(vmax);
@@ -190,40 +179,23 @@ __global__ __launch_bounds__(kTrBlock) void value_step_kernel(ValArgs A, int t, 
       atomicMax(&sl[kValMax + iter % 3], val_bits(m));
     }
   }
-  if (G_out == nullptr) return;   // (kernel argument: block-uniform)
-  // G[s] = sum_{s'} P[s, s'] V[s'] in ascending s'; P[s, s'] is wave-uniform
-  const double* Pc = A.P + rows * S;
-#pragma unroll 1
-  for (int s = wave; s < S; s += kTrWaves) {
-    double acc = 0.0;
-    for (int sp = 0; sp < S; ++sp) acc += Pc[(size_t)s * S + sp] * El[sp * kTrCols + lane];
-    if (active) G_out[(rows + s) * (size_t)n_a + j] = acc;
-  }
+  if (G_out != nullptr) tr_adjoint_mix(p, S, n_a, A.P, El, G_out);   // (kernel argument: block-uniform)
 }
 
 // W[row] = sum_j mass[row][j] V[row][j], row = (cal, s).
-__global__ __launch_bounds__(kVrBlock) void value_reduce_kernel(int n_a, const double* __restrict__ mass,
+__global__ __launch_bounds__(kTrBlock) void value_reduce_kernel(int n_a, const double* __restrict__ mass,
                                                                 const double* __restrict__ V,
                                                                 double* __restrict__ W) {
-  const int k = threadIdx.x, lane = k & (kWave - 1), wid = k / kWave;
   const size_t row = blockIdx.x;
   const double* m = mass + row * n_a;
   const double* v = V + row * n_a;
-  const int chunk = (n_a + kVrBlock - 1) / kVrBlock;
-  const long long c0 = (long long)k * chunk;
-  const int j0 = c0 < n_a ? (int)c0 : n_a;
-  const int j1 = c0 + chunk < n_a ? (int)(c0 + chunk) : n_a;
+  int j0, j1;
+  row_chunk(n_a, threadIdx.x, j0, j1);
   double acc = 0.0;
   for (int j = j0; j < j1; ++j) acc += m[j] * v[j];
-  __shared__ double s_wave[kVrWaves];
-  const double ws = wave_sum_lane63(acc);
-  if (lane == kWave - 1) s_wave[wid] = ws;
-  __syncthreads();
-  if (k == 0) {
-    double tot = 0.0;
-    for (int q = 0; q < kVrWaves; ++q) tot += s_wave[q];
-    W[row] = tot;
-  }
+  __shared__ double s_wave[kTrWaves];
+  const double tot = row_block_sum(acc, s_wave);
+  if (threadIdx.x == 0) W[row] = tot;
 }
 
 __global__ __launch_bounds__(256) void value_ce_kernel(size_t n, size_t per, const double* __restrict__ V_new,
@@ -247,22 +219,14 @@ struct ValLayout {
 };
 
 static ValLayout val_layout(int n_cal, int S, int n_a) {
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   ValLayout L;
   L.per = (size_t)n_cal * S * n_a;
-  L.nblk = (n_a + kTrCols - 1) / kTrCols;
+  L.nblk = tr_nblk(n_a);
   size_t o = 0;
-  L.g = o;     o += up(2 * L.per * sizeof(double));
-  L.slots = o; o += up((size_t)n_cal * kValSlots * sizeof(unsigned long long));
+  L.g = o;     o += tab_align(2 * L.per * sizeof(double));
+  L.slots = o; o += tab_align((size_t)n_cal * kValSlots * sizeof(unsigned long long));
   L.total = o;
   return L;
-}
-
-static int32_t val_check(aiy_handle* h, int n_cal, int S, int n_a) {
-  if (n_a < 2) return fail(h, AIY_ERR_ARG, "n_a=%d must be >= 2", n_a);
-  if (S < 1 || S > AIY_MAX_STATES) return fail(h, AIY_ERR_ARG, "S=%d outside 1..%d", S, AIY_MAX_STATES);
-  if (!tr_pull_sizes_ok(n_cal, S, n_a)) return fail(h, AIY_ERR_ARG, "bad sizes n_cal=%d S=%d n_a=%d", n_cal, S, n_a);
-  return AIY_OK;
 }
 
 static void launch_mix(const ValArgs& A, int n_cal, int nblk, const double* V, double* G, hipStream_t st) {
@@ -287,7 +251,7 @@ extern "C" int32_t aiy_value_backward(aiy_handle* h, int32_t n_cal, int32_t S, i
                                       double* V_path_out, aiy_stream stream) {
   if (!h) return AIY_ERR_ARG;
   if (T < 1) return fail(h, AIY_ERR_ARG, "T=%d must be >= 1", T);
-  int32_t rc = val_check(h, n_cal, S, n_a);
+  int32_t rc = tr_check(h, n_cal, S, n_a);
   if (rc) return rc;
   if (!lo || !wlo || !P || !a_grid || !R || !w || !lab || !beta || !crra) return fail(h, AIY_ERR_ARG, "null model array");
   if (!V_term || !work || !V0_out) return fail(h, AIY_ERR_ARG, "null buffer");
@@ -319,7 +283,7 @@ extern "C" int32_t aiy_value_stationary(aiy_handle* h, int32_t n_cal, int32_t S,
                                         double* V, void* work, int32_t* iters_out, double* dist_out,
                                         aiy_stream stream) {
   if (!h) return AIY_ERR_ARG;
-  int32_t rc = val_check(h, n_cal, S, n_a);
+  int32_t rc = tr_check(h, n_cal, S, n_a);
   if (rc) return rc;
   if (!(tol >= 1e-13)) return fail(h, AIY_ERR_ARG, "tol=%g must be >= 1e-13 (rounding moves V by more per step)", tol);
   if (max_iter < 1) return fail(h, AIY_ERR_ARG, "max_iter=%d must be >= 1", max_iter);
@@ -368,7 +332,7 @@ extern "C" int32_t aiy_value_stationary(aiy_handle* h, int32_t n_cal, int32_t S,
 extern "C" int32_t aiy_value_reduce(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, const double* mass,
                                     const double* V, double* W_out, aiy_stream stream) {
   if (!h) return AIY_ERR_ARG;
-  int32_t rc = val_check(h, n_cal, S, n_a);
+  int32_t rc = tr_check(h, n_cal, S, n_a);
   if (rc) return rc;
   if (!mass || !V || !W_out) return fail(h, AIY_ERR_ARG, "null buffer");
   AIY_HIP(h, hipSetDevice(h->device));
@@ -382,7 +346,7 @@ extern "C" int32_t aiy_value_reduce(aiy_handle* h, int32_t n_cal, int32_t S, int
     AIY_HIP(h, hipMalloc((void**)&h->d_welf, n_rows * sizeof(double)));
     h->welf_cap = n_rows;
   }
-  hipLaunchKernelGGL(value_reduce_kernel, dim3((unsigned)n_rows), dim3(kVrBlock), 0, st, n_a, mass, V, h->d_welf);
+  hipLaunchKernelGGL(value_reduce_kernel, dim3((unsigned)n_rows), dim3(kTrBlock), 0, st, n_a, mass, V, h->d_welf);
   AIY_CHECK_LAUNCH(h);
   AIY_HIP(h, hipMemcpyAsync(W_out, h->d_welf, n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
   AIY_HIP(h, hipStreamSynchronize(st));

@@ -165,10 +165,7 @@ def histogram_stats(mass, a_grid, percentiles=None, marginal=False, slab=None, d
     if slab is None:
         slab = max(1, SLAB_BYTES // (16 * n_a))
     slab = max(1, min(int(slab), n_dist))
-    nbytes = int(h.lib.aiy_dist_stats_work_bytes(slab, n_a))
-    if nbytes < 0:
-        raise ValueError(f"sizes not supported: n_dist={slab} n_a={n_a}")
-    work = torch.empty(nbytes, dtype=torch.uint8, device=m.device)
+    work = _lib.work_space(m.device, "dist_stats", "", n_dist=slab, n_a=n_a)
     lor = np.empty((n_dist, p.size))
     pct = np.empty((n_dist, p.size))
     summ = np.empty((n_dist, 4))

@@ -87,6 +87,13 @@ def path_prices(K, Z, alpha, delta):
     return r, w
 
 
+def _device(x, dev):
+    """A device tensor as it is; anything else as a float64 tensor on ``dev``."""
+    if torch.is_tensor(x):
+        return x
+    return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+
+
 def _tables(t, n_cal, S, n_a):
     """A [n_cal][S][n_a+1] view of policy tables given with or without the n_M = 1 axis."""
     t = t.reshape(n_cal, S, n_a + 1)
@@ -112,13 +119,9 @@ class TransitionBuffers:
 
     def __init__(self, batch: StationaryBatch, T: int, marginals: bool = False):
         n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
-        h = _lib.handle(batch.device.index)
-        nbytes = int(h.lib.aiy_transition_work_bytes(n_cal, S, n_a, int(T)))
-        if nbytes < 0:
-            raise ValueError(f"transition sizes not supported: n_cal={n_cal} S={S} n_a={n_a} T={T}")
         dev = batch.device
         self.T = int(T)
-        self.work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.work = _lib.work_space(dev, "transition", "transition", n_cal=n_cal, S=S, n_a=n_a, T=self.T)
         self.lo = torch.empty((self.T, n_cal, S, n_a), dtype=torch.int32, device=dev)
         self.wlo = torch.empty((self.T, n_cal, S, n_a), dtype=F64, device=dev)
         self.m0 = torch.empty((n_cal, S, n_a + 1), dtype=F64, device=dev)
@@ -176,8 +179,7 @@ def household_block(batch, R, w, m_term, c_term, mass0, want_c=True, export_poli
     the marginal over assets of every period's mass (``path_wealth_stats`` reads it)."""
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     dev = batch.device
-    dR = torch.as_tensor(np.ascontiguousarray(R, dtype=np.float64)).to(dev) if not torch.is_tensor(R) else R
-    dw = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float64)).to(dev) if not torch.is_tensor(w) else w
+    dR, dw = _device(R, dev), _device(w, dev)
     if dR.shape != dw.shape or dR.dim() != 2 or dR.shape[0] != n_cal or dR.shape[1] < 2:
         raise ValueError(f"price paths must be [n_cal][T+1], got {tuple(dR.shape)} and {tuple(dw.shape)}")
     T = dR.shape[1] - 1
@@ -189,8 +191,7 @@ def household_block(batch, R, w, m_term, c_term, mass0, want_c=True, export_poli
         buffers.marg = torch.empty((T + 1, n_cal, n_a), dtype=F64, device=dev)
     m_term = _tables(m_term, n_cal, S, n_a)
     c_term = _tables(c_term, n_cal, S, n_a)
-    if not torch.is_tensor(mass0):
-        mass0 = torch.as_tensor(np.ascontiguousarray(mass0, dtype=np.float64)).to(dev)
+    mass0 = _device(mass0, dev)
     transition_backward(batch, dR, dw, m_term, c_term, buffers, export_policy=export_policy, stream=stream)
     buffers.mass.copy_(mass0.reshape(n_cal, S, n_a))
     Ks, C = transition_forward(batch, buffers.lo, buffers.wlo, buffers.mass, T, buffers.work, dR, dw, want_c=want_c,
@@ -268,17 +269,13 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
         m_term, c_term = batch.last_tables
     if mass0 is None:
         mass0 = batch.mass
-    if not torch.is_tensor(mass0):
-        mass0 = torch.as_tensor(np.ascontiguousarray(mass0, dtype=np.float64)).to(batch.device)
-    mass0 = mass0.reshape(n_cal, S, n_a).clone()
+    mass0 = _device(mass0, batch.device).reshape(n_cal, S, n_a).clone()
     K0 = np.sum(mass0.cpu().numpy() * batch.aGrid[:, None, :], axis=(1, 2))
     K = np.repeat(K0[:, None], T + 1, axis=1)
     newton = None
     if method == "newton":
         if jacobian is None:
-            Ks = np.sum(batch.mass.cpu().numpy() * batch.aGrid[:, None, :], axis=(1, 2))
-            rs, _ = path_prices(Ks[:, None], np.ones((n_cal, 1)), batch.alpha, batch.delta)
-            jacobian = household_jacobian(batch, rs[:, 0], T, m_term=m_term, c_term=c_term)
+            jacobian = household_jacobian(batch, steady_rate(batch), T, m_term=m_term, c_term=c_term)
         if jacobian.JR.shape != (n_cal, T, T + 1):
             raise ValueError(f"jacobian holds {jacobian.JR.shape}, the solve needs {(n_cal, T, T + 1)}")
         newton = jacobian.solver()
@@ -325,6 +322,37 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
         gains = _welfare.welfare(batch, V, V_base, mass0)
     return TransitionResult(K=K, r=r, w=w, C=C, iterations=iterations, residual=residual, status=status,
                             stats=path_stats, welfare=gains)
+
+
+def steady_rate(batch):
+    """r* [n_cal]: the firm's rate at K* = sum batch.mass a."""
+    K = np.sum(batch.mass.cpu().numpy() * batch.aGrid[:, None, :], axis=(1, 2))
+    rs, _ = path_prices(K[:, None], np.ones((len(K), 1)), batch.alpha, batch.delta)
+    return rs[:, 0]
+
+
+def steady_lottery(batch, r=None, tables=None, lo=None, wlo=None):
+    """The steady state's lottery and prices on device: ``(lo, wlo, R [n_cal], w [n_cal])`` by
+    aiy_hist_lottery from ``tables`` (default ``batch.last_tables``) at the rate ``r`` (default
+    ``steady_rate(batch)``), into ``lo`` / ``wlo`` [n_cal][S][n_a] where they are given."""
+    n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
+    dev = batch.device
+    if tables is None:
+        if getattr(batch, "last_tables", None) is None:
+            raise ValueError("no steady-state policy: run steady_state / capital_supply first")
+        tables = batch.last_tables
+    m, c = (_tables(t, n_cal, S, n_a) for t in tables)
+    r = np.broadcast_to(np.asarray(steady_rate(batch) if r is None else r, dtype=np.float64), (n_cal,))
+    w, _ = firm_prices(r, batch.alpha, batch.delta)
+    dR, dw = _device(1.0 + r, dev), _device(w, dev)
+    if lo is None:
+        lo = torch.empty((n_cal, S, n_a), dtype=torch.int32, device=dev)
+        wlo = torch.empty((n_cal, S, n_a), dtype=F64, device=dev)
+    h = _lib.handle(dev.index)
+    h.check(h.lib.aiy_hist_lottery(h.h, n_cal, S, n_a, _lib.ptr(m), _lib.ptr(c), _lib.ptr(batch.d_a), _lib.ptr(dR),
+                                   _lib.ptr(dw), _lib.ptr(batch.d_lab), _lib.ptr(lo), _lib.ptr(wlo),
+                                   _lib.stream_ptr()), "aiy_hist_lottery")
+    return lo, wlo, dR, dw
 
 
 # -------------------------------------------------------------------------------------
@@ -379,13 +407,9 @@ class JacobianBuffers:
 
     def __init__(self, batch: StationaryBatch, T: int):
         n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
-        hd = _lib.handle(batch.device.index)
-        nbytes = int(hd.lib.aiy_jacobian_work_bytes(n_cal, S, n_a, int(T)))
-        if nbytes < 0:
-            raise ValueError(f"Jacobian sizes not supported: n_cal={n_cal} S={S} n_a={n_a} T={T}")
         dev = batch.device
         self.T = int(T)
-        self.work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.work = _lib.work_space(dev, "jacobian", "Jacobian", n_cal=n_cal, S=S, n_a=n_a, T=self.T)
         self.sweep = TransitionBuffers(batch, self.T + 1)
         self.ghost = torch.empty((self.T + 1, n_cal, S, n_a), dtype=F64, device=dev)
         self.dD = [torch.empty_like(self.ghost), torch.empty_like(self.ghost)]   # R, w
@@ -490,10 +514,7 @@ def household_jacobian(batch, r, T, h=1e-5, m_term=None, c_term=None, buffers=No
         hd.check(hd.lib.aiy_jacobian_diff(hd.h, buffers.ghost.numel(), _lib.ptr(buffers.dD[x]),
                                           _lib.ptr(buffers.ghost), float(h), _lib.stream_ptr()), "aiy_jacobian_diff")
         stage("diff")
-    dR, dw = torch.as_tensor(Rs.copy()).to(dev), torch.as_tensor(np.ascontiguousarray(w)).to(dev)
-    hd.check(hd.lib.aiy_hist_lottery(hd.h, n_cal, S, n_a, _lib.ptr(m_term), _lib.ptr(c_term), _lib.ptr(batch.d_a),
-                                     _lib.ptr(dR), _lib.ptr(dw), _lib.ptr(batch.d_lab), _lib.ptr(buffers.lo),
-                                     _lib.ptr(buffers.wlo), _lib.stream_ptr()), "aiy_hist_lottery")
+    steady_lottery(batch, r, tables=(m_term, c_term), lo=buffers.lo, wlo=buffers.wlo)
     jacobian_expectation(batch, buffers.lo, buffers.wlo, buffers.E, buffers.work)
     stage("expectation")
     jacobian_contract(dev, buffers.E, buffers.dD[0], buffers.dD[1], buffers.work, F=buffers.F)

@@ -34,25 +34,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from .stationary import firm_prices
-from .transition import _tables, path_prices
+from .transition import _device, steady_lottery  # noqa: F401  (steady_lottery: also imported from here)
 
 F64 = torch.float64
 
 
-def _device(x, dev):
-    if torch.is_tensor(x):
-        return x
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
-
-
 def _work(batch):
-    n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
-    h = _lib.handle(batch.device.index)
-    nbytes = int(h.lib.aiy_value_work_bytes(n_cal, S, n_a))
-    if nbytes < 0:
-        raise ValueError(f"value sizes not supported: n_cal={n_cal} S={S} n_a={n_a}")
-    return torch.empty(nbytes, dtype=torch.uint8, device=batch.device)
+    return _lib.work_space(batch.device, "value", "value", n_cal=len(batch.cals), S=batch.S, n_a=batch.n_a)
 
 
 def path_value(batch, lo, wlo, R, w, V_term, keep_path=False, work=None, stream=None):
@@ -83,32 +71,6 @@ def path_value(batch, lo, wlo, R, w, V_term, keep_path=False, work=None, stream=
                                      _lib.ptr(work), _lib.ptr(V0), _lib.ptr(V_path), _lib.stream_ptr(stream)),
             "aiy_value_backward")
     return (V0, V_path) if keep_path else V0
-
-
-def steady_lottery(batch, r=None):
-    """The steady state's lottery and prices on device: ``(lo, wlo, R [n_cal], w [n_cal])`` from
-    ``batch.last_tables`` by aiy_hist_lottery, as ``household_jacobian`` builds it.  ``r``
-    defaults to the firm's rate at K* = sum batch.mass a."""
-    n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
-    dev = batch.device
-    if getattr(batch, "last_tables", None) is None:
-        raise ValueError("no steady-state policy: run steady_state / capital_supply first")
-    m, c = (_tables(t, n_cal, S, n_a) for t in batch.last_tables)
-    if r is None:
-        K = np.sum(batch.mass.cpu().numpy() * batch.aGrid[:, None, :], axis=(1, 2))
-        rs, _ = path_prices(K[:, None], np.ones((n_cal, 1)), batch.alpha, batch.delta)
-        r = rs[:, 0]
-    r = np.broadcast_to(np.asarray(r, dtype=np.float64), (n_cal,))
-    w, _ = firm_prices(r, batch.alpha, batch.delta)
-    dR = torch.as_tensor(1.0 + r).to(dev)
-    dw = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float64)).to(dev)
-    lo = torch.empty((n_cal, S, n_a), dtype=torch.int32, device=dev)
-    wlo = torch.empty((n_cal, S, n_a), dtype=F64, device=dev)
-    h = _lib.handle(dev.index)
-    h.check(h.lib.aiy_hist_lottery(h.h, n_cal, S, n_a, _lib.ptr(m), _lib.ptr(c), _lib.ptr(batch.d_a), _lib.ptr(dR),
-                                   _lib.ptr(dw), _lib.ptr(batch.d_lab), _lib.ptr(lo), _lib.ptr(wlo),
-                                   _lib.stream_ptr()), "aiy_hist_lottery")
-    return lo, wlo, dR, dw
 
 
 def stationary_value(batch, r=None, tol=1e-10, max_iter=5000, chunk=0, info=None):
