@@ -20,7 +20,7 @@ SOURCES = ["api.hip", "index.hip", "egm.hip", "panel_tab.hip", "panel.hip", "pan
            "hist.hip", "hist_resident.hip", "hist_krylov.hip", "stats.hip", "ge.hip", "ge_resident.hip", "hooks.hip",
            "transition.hip", "transition_jac.hip", "dist_stats.hip", "welfare.hip"]
 HEADERS = ["common.h", "internal.h", "panel_common.h", "hist_cluster.h", "egm_common.h", "hist_bicg.h", "ge_search.h",
-           "hist_pull.h", "transition_common.h"]
+           "hist_pull.h", "transition_common.h", "carve.h", "owned.h", "hist_scratch.h"]
 ARCH = os.environ.get("AIY_OFFLOAD_ARCH", "gfx950")
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-result",
           "-I/opt/rocm/include"]

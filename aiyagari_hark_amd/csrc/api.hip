@@ -27,36 +27,7 @@ extern "C" int32_t aiy_destroy(aiy_handle* h) {
   if (!h) return AIY_OK;
   (void)hipSetDevice(h->device);
   if (h->comm && h->comm_owned) (void)ncclCommDestroy(h->comm);
-  if (h->d_dist) (void)hipFree(h->d_dist);
-  if (h->d_last) (void)hipFree(h->d_last);
-  if (h->d_egm_hint) (void)hipFree(h->d_egm_hint);
-  if (h->d_egm_aa) (void)hipFree(h->d_egm_aa);
-  if (h->h_dist) (void)hipHostFree(h->h_dist);
-  if (h->h_last) (void)hipHostFree(h->h_last);
-  if (h->d_partials) (void)hipFree(h->d_partials);
-  if (h->d_ticket) (void)hipFree(h->d_ticket);
   if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
-  if (h->d_blk) (void)hipFree(h->d_blk);
-  if (h->d_res_sync) (void)hipFree(h->d_res_sync);
-  for (hipEvent_t e : h->res_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->h_blk) (void)hipHostFree(h->h_blk);
-  if (h->d_hdist) (void)hipFree(h->d_hdist);
-  if (h->d_K) (void)hipFree(h->d_K);
-  if (h->d_hlast) (void)hipFree(h->d_hlast);
-  if (h->d_stats) (void)hipFree(h->d_stats);
-  if (h->d_welf) (void)hipFree(h->d_welf);
-  if (h->h_hdist) (void)hipHostFree(h->h_hdist);
-  if (h->h_K) (void)hipHostFree(h->h_K);
-  if (h->h_hlast) (void)hipHostFree(h->h_hlast);
-  if (h->hand_ev) (void)hipEventDestroy(h->hand_ev);
-  if (h->d_ge) (void)hipFree(h->d_ge);
-  for (hipEvent_t e : h->ge_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->d_hc) (void)hipFree(h->d_hc);
-  if (h->d_hcd) (void)hipFree(h->d_hcd);
-  for (hipEvent_t e : h->hc_ev)
-    if (e) (void)hipEventDestroy(e);
   delete h;
   return AIY_OK;
 }

@@ -189,17 +189,17 @@ __global__ __launch_bounds__(kDsBlock) void dist_stats_kernel(DsArgs A) {
 
 // Work space (caller-owned): [cw | cd of every distribution][percentiles][results], every
 // region on a 256-byte boundary; the results region holds kDsMaxPct percentiles.
-struct DsLayout {
-  size_t cum, pct, res, total;   // byte offsets
+struct DsWork {
+  double *cum, *pct, *res;
+  size_t bytes;
 };
 static bool ds_sizes_ok(int n_dist, int n_a) { return n_dist >= 1 && n_a >= 2; }
-static DsLayout ds_layout(int n_dist, int n_a) {
-  DsLayout L;
-  size_t o = 0;
-  L.cum = o; o += tab_align((size_t)n_dist * 2 * n_a * sizeof(double));
-  L.pct = o; o += tab_align(kDsMaxPct * sizeof(double));
-  L.res = o; o += tab_align((size_t)n_dist * (2 * kDsMaxPct + kDsSummary) * sizeof(double));
-  L.total = o;
+static DsWork ds_work(Carve c, int n_dist, int n_a) {
+  DsWork L;
+  L.cum = c.take<double>((size_t)n_dist * 2 * n_a);
+  L.pct = c.take<double>(kDsMaxPct);
+  L.res = c.take<double>((size_t)n_dist * (2 * kDsMaxPct + kDsSummary));
+  L.bytes = c.bytes();
   return L;
 }
 
@@ -209,7 +209,7 @@ using namespace aiy;
 
 extern "C" int64_t aiy_dist_stats_work_bytes(int32_t n_dist, int32_t n_a) {
   if (!ds_sizes_ok(n_dist, n_a)) return -1;
-  return (int64_t)ds_layout(n_dist, n_a).total;
+  return (int64_t)ds_work(Carve(), n_dist, n_a).bytes;
 }
 
 extern "C" int32_t aiy_dist_marginal(aiy_handle* h, int32_t n_dist, int32_t S, int32_t n_a, const double* mass,
@@ -238,20 +238,19 @@ extern "C" int32_t aiy_dist_stats(aiy_handle* h, int32_t n_dist, int32_t n_grid,
   if (!g || !a_grid || !work) return fail(h, AIY_ERR_ARG, "null buffer");
   AIY_HIP(h, hipSetDevice(h->device));
   hipStream_t st = as_stream(stream);
-  const DsLayout L = ds_layout(n_dist, n_a);
-  char* wb = static_cast<char*>(work);
+  const DsWork L = ds_work(Carve(work), n_dist, n_a);
   const size_t n_res = (size_t)n_dist * n_p;
-  double* d_res = reinterpret_cast<double*>(wb + L.res);   // lorenz | percentiles | summary, packed
+  double* d_res = L.res;   // lorenz | percentiles | summary, packed
   DsArgs A;
   A.n_grid = n_grid; A.n_a = n_a; A.n_p = n_p;
   A.g = g; A.a_grid = a_grid;
-  A.pct = reinterpret_cast<double*>(wb + L.pct);
-  A.cum = reinterpret_cast<double*>(wb + L.cum);
+  A.pct = L.pct;
+  A.cum = L.cum;
   A.lorenz = d_res;
   A.pctl = d_res + n_res;
   A.summary = d_res + 2 * n_res;
   if (n_p > 0)
-    AIY_HIP(h, hipMemcpyAsync(wb + L.pct, pctiles, n_p * sizeof(double), hipMemcpyHostToDevice, st));
+    AIY_HIP(h, hipMemcpyAsync(L.pct, pctiles, n_p * sizeof(double), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(dist_stats_kernel, dim3((unsigned)n_dist), dim3(kDsBlock), 0, st, A);
   AIY_CHECK_LAUNCH(h);
   std::vector<double> res(2 * n_res + (size_t)n_dist * kDsSummary);   // heap: n_dist x n_p results

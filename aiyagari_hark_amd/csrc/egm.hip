@@ -582,35 +582,32 @@ static int32_t egm_hints(aiy_handle* h, const EgmDev& A, hipStream_t st, int** o
   const size_t ints = (size_t)n_work * egm_rows(A) * A.S;
   const unsigned long long sig = ((unsigned long long)A.n_cal << 48) ^ ((unsigned long long)A.S << 40) ^
                                  ((unsigned long long)A.n_M << 24) ^ (unsigned long long)A.n_a;
-  if (ints > h->egm_hint_cap) {
-    if (h->d_egm_hint) (void)hipFree(h->d_egm_hint);
-    h->d_egm_hint = nullptr;
-    h->egm_hint_cap = 0;
-    AIY_HIP(h, hipMalloc((void**)&h->d_egm_hint, ints * sizeof(int)));
-    h->egm_hint_cap = ints;
-    h->egm_hint_sig = ~0ull;
-  }
+  bool grew = false;
+  const int32_t rc = h->egm_hint.reserve(h, ints * sizeof(int), &grew);
+  if (rc) return rc;
+  if (grew) h->egm_hint_sig = ~0ull;
   if (sig != h->egm_hint_sig) {
-    AIY_HIP(h, hipMemsetAsync(h->d_egm_hint, 0xFF, ints * sizeof(int), st));
+    AIY_HIP(h, hipMemsetAsync(h->egm_hint.as<int>(), 0xFF, ints * sizeof(int), st));
     h->egm_hint_sig = sig;
   }
-  *out = h->d_egm_hint;
+  *out = h->egm_hint.as<int>();
   return AIY_OK;
 }
 
-static int32_t ensure_egm_scratch(aiy_handle* h, int n_cal) {
-  if ((size_t)n_cal <= h->egm_cap) return AIY_OK;
-  if (h->d_dist) { (void)hipFree(h->d_dist); (void)hipFree(h->d_last); }
-  if (h->h_dist) { (void)hipHostFree(h->h_dist); (void)hipHostFree(h->h_last); }
-  h->d_dist = nullptr; h->d_last = nullptr; h->h_dist = nullptr; h->h_last = nullptr; h->egm_cap = 0;
-  // + n_cal doubles behind the slots: the extrapolation factors (device and pinned host)
-  AIY_HIP(h, hipMalloc((void**)&h->d_dist, sizeof(unsigned long long) * (kSlots + 1) * n_cal));
-  AIY_HIP(h, hipMalloc((void**)&h->d_last, sizeof(int) * n_cal));
-  AIY_HIP(h, hipHostMalloc((void**)&h->h_dist, sizeof(unsigned long long) * (kSlots + 1) * n_cal,
-                           hipHostMallocDefault));
-  AIY_HIP(h, hipHostMalloc((void**)&h->h_last, sizeof(int) * n_cal, hipHostMallocDefault));
-  h->egm_cap = n_cal;
-  return AIY_OK;
+// Convergence slots of a solve: the same layout on the device and in the pinned host mirror.
+struct EgmSlots {
+  unsigned long long* dist;   // [n_cal][kSlots]
+  double* factor;             // [n_cal] extrapolation factors
+  int* last;                  // [n_cal]
+  size_t bytes;
+};
+static EgmSlots egm_slots(Carve c, int n_cal) {
+  EgmSlots L;
+  L.dist = c.take<unsigned long long>((size_t)kSlots * n_cal);
+  L.factor = c.take<double>(n_cal);
+  L.last = c.take<int>(n_cal);
+  L.bytes = c.bytes();
+  return L;
 }
 
 }  // namespace aiy
@@ -725,8 +722,12 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
   if (max_cycles < 1) return fail(h, AIY_ERR_ARG, "max_cycles must be >= 1");
   if (chunk <= 0) chunk = 32;
   AIY_HIP(h, hipSetDevice(h->device));
-  rc = ensure_egm_scratch(h, dims->n_cal);
+  const size_t slot_bytes = egm_slots(Carve(), dims->n_cal).bytes;
+  rc = h->egm_dev.reserve(h, slot_bytes);
+  if (rc == AIY_OK) rc = h->egm_pin.reserve(h, slot_bytes);
   if (rc) return rc;
+  const EgmSlots dv = egm_slots(Carve(h->egm_dev.get()), dims->n_cal);
+  const EgmSlots hv = egm_slots(Carve(h->egm_pin.get()), dims->n_cal);
   hipStream_t st = as_stream(stream);
   AIY_USE_STREAM(h, st);
   const int n_cal = dims->n_cal;
@@ -738,8 +739,8 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
   int* hints = nullptr;
   rc = egm_hints(h, A, st, &hints);
   if (rc) return rc;
-  AIY_HIP(h, hipMemsetAsync(h->d_dist, 0, sizeof(unsigned long long) * kSlots * n_cal, st));
-  AIY_HIP(h, hipMemsetAsync(h->d_last, 0, sizeof(int) * n_cal, st));
+  AIY_HIP(h, hipMemsetAsync(dv.dist, 0, sizeof(unsigned long long) * kSlots * n_cal, st));
+  AIY_HIP(h, hipMemsetAsync(dv.last, 0, sizeof(int) * n_cal, st));
   const bool warm = m_init != nullptr;
   if (warm) {   // cycle 0 = the caller's tables (ping-pong slot 0)
     AIY_HIP(h, hipMemcpyAsync(work_m, m_init, buf * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -757,14 +758,9 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
   if (aa) {
     chunk = h->ge_anderson;
     const size_t need = 5 * buf + (size_t)n_cal * kEgmAaBlocks * 9 + (size_t)n_cal * 4;
-    if (need > h->egm_aa_cap) {
-      if (h->d_egm_aa) (void)hipFree(h->d_egm_aa);
-      h->d_egm_aa = nullptr;
-      h->egm_aa_cap = 0;
-      AIY_HIP(h, hipMalloc((void**)&h->d_egm_aa, need * sizeof(double)));
-      h->egm_aa_cap = need;
-    }
-    ring = h->d_egm_aa;
+    rc = h->egm_aa.reserve(h, need * sizeof(double));
+    if (rc) return rc;
+    ring = h->egm_aa.as<double>();
     d_part = ring + 5 * buf;
     d_gam = d_part + (size_t)n_cal * kEgmAaBlocks * 9;
   }
@@ -774,8 +770,8 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
   cloc[0] = work_c;
   std::vector<double> lam_prev(n_cal, -1.0);
   std::vector<char> moved(n_cal, 0);
-  double* hf = reinterpret_cast<double*>(h->h_dist + (size_t)kSlots * n_cal);
-  double* df = reinterpret_cast<double*>(h->d_dist + (size_t)kSlots * n_cal);
+  double* hf = hv.factor;
+  double* df = dv.factor;
   while (true) {
     const int end = std::min(next + chunk, last_allowed + 1);
     for (int cyc = next; cyc < end; ++cyc) {
@@ -786,17 +782,17 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
       // converged calibration's cycles write nothing, so its tables stay where they were written
       double* co = (aa && cyc >= end - 5) ? ring + (size_t)(cyc % 5) * buf : work_c + (cyc & 1) * buf;
       cloc[cyc] = co;
-      launch_cycle(A, mn, cn, work_m + (cyc & 1) * buf, co, hints, cyc, h->d_dist, h->d_last, tol, st);
+      launch_cycle(A, mn, cn, work_m + (cyc & 1) * buf, co, hints, cyc, dv.dist, dv.last, tol, st);
     }
     AIY_CHECK_LAUNCH(h);
-    AIY_HIP(h, hipMemcpyAsync(h->h_last, h->d_last, sizeof(int) * n_cal, hipMemcpyDeviceToHost, st));
-    AIY_HIP(h, hipMemcpyAsync(h->h_dist, h->d_dist, sizeof(unsigned long long) * kSlots * n_cal, hipMemcpyDeviceToHost, st));
+    AIY_HIP(h, hipMemcpyAsync(hv.last, dv.last, sizeof(int) * n_cal, hipMemcpyDeviceToHost, st));
+    AIY_HIP(h, hipMemcpyAsync(hv.dist, dv.dist, sizeof(unsigned long long) * kSlots * n_cal, hipMemcpyDeviceToHost, st));
     AIY_HIP(h, hipStreamSynchronize(st));
     bool all = true;
     std::vector<char> conv(n_cal, 0);
     for (int c = 0; c < n_cal; ++c) {
-      const int last = h->h_last[c];
-      const double d = slot_max(h->h_dist + (size_t)c * kSlots, last);
+      const int last = hv.last[c];
+      const double d = slot_max(hv.dist + (size_t)c * kSlots, last);
       conv[c] = (last >= 2 && !(d > tol_of(c))) || last >= last_allowed;
       all = all && conv[c];
     }
@@ -807,7 +803,7 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
       const int L = end - 1;   // the last launched cycle: w4 (its tables in slot L & 1)
       bool any = false;
       // (a calibration still running at L, whose last five cycles all ran in this chunk)
-      auto mixable = [&](int c) { return !conv[c] && h->h_last[c] == L && end - start >= 5; };
+      auto mixable = [&](int c) { return !conv[c] && hv.last[c] == L && end - start >= 5; };
       for (int c = 0; c < n_cal; ++c) any = any || mixable(c);
       if (any) {
         const long long per = (long long)per_cal;
@@ -842,11 +838,11 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
       bool any = false;
       for (int c = 0; c < n_cal; ++c) {
         hf[c] = 0.0;
-        if (h->h_last[c] != L || L < 4) {
+        if (hv.last[c] != L || L < 4) {
           lam_prev[c] = -1.0;
           continue;
         }
-        const unsigned long long* sl = h->h_dist + (size_t)c * kSlots;
+        const unsigned long long* sl = hv.dist + (size_t)c * kSlots;
         hf[c] = egm_extrap_factor(slot_max(sl, L), slot_max(sl, L - 1), tol_of(c), L, lam_prev[c]);
         if (hf[c] != 0.0) {
           moved[c] = 1;
@@ -867,8 +863,8 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
   if (extrap) {   // an extrapolated calibration that ended in NaN: the whole solve again, plain
     bool bad = false;
     for (int c = 0; c < n_cal; ++c) {
-      const int last = h->h_last[c];
-      const double d = slot_max(h->h_dist + (size_t)c * kSlots, last);
+      const int last = hv.last[c];
+      const double d = slot_max(hv.dist + (size_t)c * kSlots, last);
       bad = bad || (moved[c] && d != d);
     }
     if (bad) {
@@ -880,8 +876,8 @@ int32_t aiy_egm_solve_impl(aiy_handle* h, const aiy_egm_dims* dims, const aiy_eg
     }
   }
   for (int c = 0; c < n_cal; ++c) {
-    const int last = h->h_last[c];
-    const double d = slot_max(h->h_dist + (size_t)c * kSlots, last);
+    const int last = hv.last[c];
+    const double d = slot_max(hv.dist + (size_t)c * kSlots, last);
     cycles_out[c] = last;
     dist_out[c] = last >= 2 ? d : 100.0;
     const size_t off = (size_t)c * per_cal;

@@ -59,22 +59,26 @@ __global__ void secant_start_kernel(long long per, int n_cal, const double* __re
   }
 }
 
-struct GeLayout {
-  size_t Rn, Wn, Mn, Mg, Rc, wc, tm, tc, wm, wc2, lo, wlo, mass, hw, pm, pc, im, ic, pmass, th, etol, htol, bytes;
+// The caller's work space of the host-driven search.
+struct GeWork {
+  double *Rn, *Wn, *Mn, *Mg, *Rc, *wc, *tm, *tc, *wm, *wc2, *wlo, *mass, *hw, *pmass, *th;
+  double *pm, *pc, *im, *ic;   // previous evaluation's tables, secant starts
+  double *etol, *htol;         // loose bracketing: per-calibration tolerances of this step (GeEval::plan, ge_search.h)
+  int32_t* lo;
+  size_t bytes;
 };
-static GeLayout ge_layout(int n_cal, int S, int n_a) {
-  GeLayout L;
+static GeWork ge_work(Carve c, int n_cal, int S, int n_a) {
+  GeWork L;
   const size_t ns = (size_t)n_cal * S, tab = ns * (n_a + 1), pts = ns * n_a;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-  L.Rn = take(ns * 8); L.Wn = take(ns * 8); L.Mn = take(ns * 8); L.Mg = take((size_t)n_cal * 8);
-  L.Rc = take((size_t)n_cal * 8); L.wc = take((size_t)n_cal * 8);
-  L.tm = take(tab * 8); L.tc = take(tab * 8); L.wm = take(2 * tab * 8); L.wc2 = take(2 * tab * 8);
-  L.lo = take(pts * 4); L.wlo = take(pts * 8); L.mass = take(pts * 8); L.hw = take(2 * pts * 8);
-  L.pm = take(tab * 8); L.pc = take(tab * 8); L.im = take(tab * 8); L.ic = take(tab * 8);
-  L.pmass = take(pts * 8); L.th = take((size_t)n_cal * 8);
-  L.etol = take((size_t)n_cal * 8); L.htol = take((size_t)n_cal * 8);
-  L.bytes = o;
+  auto dbl = [&](size_t n) { return c.take<double>(n); };
+  L.Rn = dbl(ns); L.Wn = dbl(ns); L.Mn = dbl(ns); L.Mg = dbl(n_cal);
+  L.Rc = dbl(n_cal); L.wc = dbl(n_cal);
+  L.tm = dbl(tab); L.tc = dbl(tab); L.wm = dbl(2 * tab); L.wc2 = dbl(2 * tab);
+  L.lo = c.take<int32_t>(pts); L.wlo = dbl(pts); L.mass = dbl(pts); L.hw = dbl(2 * pts);
+  L.pm = dbl(tab); L.pc = dbl(tab); L.im = dbl(tab); L.ic = dbl(tab);
+  L.pmass = dbl(pts); L.th = dbl(n_cal);
+  L.etol = dbl(n_cal); L.htol = dbl(n_cal);
+  L.bytes = c.bytes();
   return L;
 }
 
@@ -84,7 +88,7 @@ using namespace aiy;
 
 extern "C" int64_t aiy_ge_stationary_work_bytes(int32_t n_cal, int32_t S, int32_t n_a) {
   if (n_cal < 1 || S < 1 || n_a < 2) return -1;
-  return (int64_t)ge_layout(n_cal, S, n_a).bytes;
+  return (int64_t)ge_work(Carve(), n_cal, S, n_a).bytes;
 }
 
 extern "C" int32_t aiy_ge_stationary(aiy_handle* h, const aiy_stationary_model* M, const aiy_ge_options* o,
@@ -107,32 +111,12 @@ extern "C" int32_t aiy_ge_stationary(aiy_handle* h, const aiy_stationary_model* 
     if (rr < 0) return rr;
     if (rr == 1) return AIY_OK;
   }
-  const GeLayout L = ge_layout(n_cal, S, n_a);
-  char* base = static_cast<char*>(work);
-  double* Rn = reinterpret_cast<double*>(base + L.Rn);
-  double* Wn = reinterpret_cast<double*>(base + L.Wn);
-  double* Mn = reinterpret_cast<double*>(base + L.Mn);
-  double* Mg = reinterpret_cast<double*>(base + L.Mg);
-  double* Rc = reinterpret_cast<double*>(base + L.Rc);
-  double* wc = reinterpret_cast<double*>(base + L.wc);
-  double* tm = reinterpret_cast<double*>(base + L.tm);
-  double* tc = reinterpret_cast<double*>(base + L.tc);
-  double* wm = reinterpret_cast<double*>(base + L.wm);
-  double* wc2 = reinterpret_cast<double*>(base + L.wc2);
-  int32_t* lo = reinterpret_cast<int32_t*>(base + L.lo);
-  double* wlo = reinterpret_cast<double*>(base + L.wlo);
-  double* mass = reinterpret_cast<double*>(base + L.mass);
-  double* hw = reinterpret_cast<double*>(base + L.hw);
-  double* pm = reinterpret_cast<double*>(base + L.pm);      // previous evaluation's tables
-  double* pc = reinterpret_cast<double*>(base + L.pc);
-  double* im = reinterpret_cast<double*>(base + L.im);      // secant starts
-  double* ic = reinterpret_cast<double*>(base + L.ic);
-  double* pmass = reinterpret_cast<double*>(base + L.pmass);
-  double* d_th = reinterpret_cast<double*>(base + L.th);
+  const GeWork L = ge_work(Carve(work), n_cal, S, n_a);
+  double *Rn = L.Rn, *Wn = L.Wn, *Mn = L.Mn, *Mg = L.Mg, *Rc = L.Rc, *wc = L.wc, *tm = L.tm, *tc = L.tc, *wm = L.wm,
+         *wc2 = L.wc2, *wlo = L.wlo, *mass = L.mass, *hw = L.hw, *pm = L.pm, *pc = L.pc, *im = L.im, *ic = L.ic,
+         *pmass = L.pmass, *d_th = L.th, *d_etol = L.etol, *d_htol = L.htol;
+  int32_t* lo = L.lo;
   const long long tab_per = (long long)S * (n_a + 1), pts_per = (long long)S * n_a;
-  // loose bracketing: per-calibration tolerances of this step (GeEval::plan, ge_search.h)
-  double* d_etol = reinterpret_cast<double*>(base + L.etol);
-  double* d_htol = reinterpret_cast<double*>(base + L.htol);
   std::vector<double> theta(n_cal, 0.0), etol(n_cal, o->egm_tol), htol(n_cal, o->hist_tol);
   const bool loose_on = o->loose_bracket && o->method == 1;
   const GeEvalOpts eo{o->method, o->loose_bracket != 0, h->ge_logsec, o->warm_egm != 0, o->warm_hist != 0,

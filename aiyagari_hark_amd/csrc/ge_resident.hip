@@ -1012,14 +1012,9 @@ static bool ge_make_plan(aiy_handle* h, int n_cal, int S, int n_a, GePlan& p) {
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) return false;
   if (h->cu_limit > 0) cus = std::min(cus, h->cu_limit);
-  const int g_min = (n_a + 2 * 512 - 1) / (2 * 512);
   // the cluster reductions' sweep (hc_sweep, hist_cluster.h) reads at most kHcMaxG workgroups
-  if (g_min > kHcMaxG || g_min > cus) return false;
   const int g_cap = h->hist_cluster_cap > 0 ? h->hist_cluster_cap : 32;
-  int G = std::max(g_min, std::min(std::min(g_cap, kHcMaxG), cus / n_cal));
-  G = std::min(G, n_a);
-  p.nj = (n_a + G - 1) / G;
-  p.G = (n_a + p.nj - 1) / p.nj;
+  if (!hc_cluster_split(n_a, (n_a + 2 * 512 - 1) / (2 * 512), g_cap, cus, n_cal, &p.G, &p.nj)) return false;
   if (p.G > kHcMaxG) return false;
   if (p.nj > kGeMaxTiles * kTile) return false;
   if ((long long)p.G * n_cal > cus) return false;
@@ -1031,15 +1026,9 @@ static bool ge_make_plan(aiy_handle* h, int n_cal, int S, int n_a, GePlan& p) {
   const bool pull = h->hist_pull != 0;   // AIY_OPT_HIST_PULL: deterministic distribution solves
   if (p.sc == 7) p.fn = p.kc == 1 ? ge_fn<7, 7, 1, 512>(pull) : ge_fn<7, 7, 2, 512>(pull);
   else p.fn = p.kc == 1 ? ge_fn<8, 0, 1, 512>(pull) : ge_fn<8, 0, 2, 512>(pull);
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, p.fn) != hipSuccess) return false;
-  int lds_dev = 0;
-  if (hipDeviceGetAttribute(&lds_dev, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device) != hipSuccess)
-    return false;
-  const size_t lds_total = std::min<size_t>(kHcLdsTotal, (size_t)lds_dev);
-  const size_t stat = fa.sharedSizeBytes;
-  if (stat + 4096 >= lds_total) return false;
-  p.lds = (lds_total - stat - 1024) / 256 * 256;
+  HcLds lds;
+  if (!hc_lds_budget(h->device, p.fn, lds)) return false;
+  p.lds = lds.dyn;
   const size_t vbytes = (size_t)p.kc * p.smax * th * sizeof(double);   // BiCGSTAB v behind the spans
   const size_t egm_lds = ge_egm_lds<8>();
   if (p.lds < egm_lds || p.lds <= vbytes + 4096) return false;
@@ -1048,38 +1037,41 @@ static bool ge_make_plan(aiy_handle* h, int n_cal, int S, int n_a, GePlan& p) {
   return true;
 }
 
-struct GeScratch {
-  size_t tab, mass, pmass, pg, qb, ainv, lo, wlo, slab, span, ctr, gran, ids, saved, resume, done, err, cal, outd, outi, prof,
-      evlog, aah, bytes;
-};
 // Per-calibration arrays (kept across the rebalancing launches) first, then the per-launch
 // cluster arrays sized for the most workgroups any launch can hold (cus) and the largest span
 // capacity (cap_max doubles).
-static GeScratch ge_scratch_layout(int n_cal, int S, int n_a, int cus, int cap_max) {
+struct GeScratch {
+  double *tab, *mass, *pmass, *pg, *qb, *wlo, *slab, *outd, *prof, *evlog, *aah;
+  int *ainv, *lo, *span, *ids, *resume, *done, *outi;
+  unsigned *ctr, *err;
+  unsigned long long* gran;
+  GeState* saved;
+  GeCalDev* cal;
+  size_t bytes;
+};
+static GeScratch ge_scratch(Carve c, int n_cal, int S, int n_a, int cus, int cap_max) {
   GeScratch L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
   const size_t pts = (size_t)n_cal * S * n_a;
-  L.tab = take((size_t)n_cal * kGeBufs * 2 * S * (n_a + 1) * sizeof(double));
-  L.mass = take(pts * 8); L.pmass = take(pts * 8); L.pg = take(pts * 8); L.qb = take(pts * 8);
-  L.ainv = take((size_t)n_cal * S * (n_a + 1) * sizeof(int));
-  L.lo = take(pts * 4); L.wlo = take(pts * 8);
-  L.slab = take((size_t)cus * 2 * cap_max * sizeof(double));
-  L.span = take((size_t)cus * 8 * 4 * sizeof(int));
-  L.ctr = take((size_t)n_cal * kHcCtrStride * sizeof(unsigned));
-  L.gran = take((size_t)cus * 2 * kHcRedRec * sizeof(unsigned long long));
-  L.ids = take((size_t)n_cal * sizeof(int));
-  L.saved = take((size_t)n_cal * sizeof(GeState));
-  L.resume = take((size_t)n_cal * sizeof(int));
-  L.done = take((size_t)n_cal * sizeof(int));
-  L.err = take(256);
-  L.cal = take((size_t)n_cal * sizeof(GeCalDev));
-  L.outd = take((size_t)n_cal * 3 * sizeof(double));
-  L.outi = take((size_t)n_cal * 4 * sizeof(int));
-  L.prof = take((size_t)n_cal * kGeProf * sizeof(double));
-  L.evlog = take((size_t)n_cal * kGeEvLog * kGeEvRec * sizeof(double));
-  L.aah = take((size_t)n_cal * kGeAaHist * S * n_a * sizeof(double));
-  L.bytes = o;
+  L.tab = c.take<double>((size_t)n_cal * kGeBufs * 2 * S * (n_a + 1));
+  L.mass = c.take<double>(pts); L.pmass = c.take<double>(pts); L.pg = c.take<double>(pts); L.qb = c.take<double>(pts);
+  L.ainv = c.take<int>((size_t)n_cal * S * (n_a + 1));
+  L.lo = c.take<int>(pts); L.wlo = c.take<double>(pts);
+  L.slab = c.take<double>((size_t)cus * 2 * cap_max);
+  L.span = c.take<int>((size_t)cus * 8 * 4);
+  L.ctr = c.take<unsigned>((size_t)n_cal * kHcCtrStride);
+  L.gran = c.take<unsigned long long>((size_t)cus * 2 * kHcRedRec);
+  L.ids = c.take<int>(n_cal);
+  L.saved = c.take<GeState>(n_cal);
+  L.resume = c.take<int>(n_cal);
+  L.done = c.take<int>(n_cal);
+  L.err = c.take<unsigned>(256 / sizeof(unsigned));
+  L.cal = c.take<GeCalDev>(n_cal);
+  L.outd = c.take<double>((size_t)n_cal * 3);
+  L.outi = c.take<int>((size_t)n_cal * 4);
+  L.prof = c.take<double>((size_t)n_cal * kGeProf);
+  L.evlog = c.take<double>((size_t)n_cal * kGeEvLog * kGeEvRec);
+  L.aah = c.take<double>((size_t)n_cal * kGeAaHist * S * n_a);
+  L.bytes = c.bytes();
   return L;
 }
 
@@ -1100,15 +1092,9 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) return 0;
   if (h->cu_limit > 0) cus = std::min(cus, h->cu_limit);
   const int cap_max = (int)(kHcLdsTotal / sizeof(double));
-  const GeScratch L = ge_scratch_layout(n_cal, S, n_a, cus, cap_max);
-  if (L.bytes > h->ge_cap) {
-    if (h->d_ge) (void)hipFree(h->d_ge);
-    h->d_ge = nullptr;
-    h->ge_cap = 0;
-    AIY_HIP(h, hipMalloc(&h->d_ge, L.bytes));
-    h->ge_cap = L.bytes;
-  }
-  char* base = static_cast<char*>(h->d_ge);
+  const int32_t rsv = h->ge.reserve(h, ge_scratch(Carve(), n_cal, S, n_a, cus, cap_max).bytes);
+  if (rsv) return rsv;
+  const GeScratch L = ge_scratch(Carve(h->ge.get()), n_cal, S, n_a, cus, cap_max);
   std::vector<GeCalDev> cals(n_cal);
   for (int c = 0; c < n_cal; ++c) {
     cals[c].alpha = M->alpha[c];
@@ -1120,7 +1106,7 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
   GeRun g;
   g.n_cal = n_cal; g.S = S; g.n_a = n_a;
   g.a_grid = M->a_grid; g.P = M->P; g.lab = M->lab; g.beta = M->beta; g.crra = M->crra;
-  g.cal = reinterpret_cast<const GeCalDev*>(base + L.cal);
+  g.cal = L.cal;
   g.method = o->method; g.r_tol = o->r_tol; g.egm_tol = o->egm_tol; g.hist_tol = o->hist_tol;
   g.max_steps = o->max_steps;
   g.max_cyc = o->max_egm_cycles > 0 ? o->max_egm_cycles : 5000;
@@ -1129,41 +1115,24 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
   g.secant = o->secant_start != 0; g.loose = o->loose_bracket != 0; g.extrap = o->egm_extrapolate != 0;
   g.extrap_period = h->ge_extrap_period;
   g.aa_period = o->egm_extrapolate != 0 ? h->ge_anderson : 0;   // (with the EGM acceleration on)
-  g.aah = reinterpret_cast<double*>(base + L.aah);
+  g.aah = L.aah;
   g.logsec = h->ge_logsec;
-  g.tab = reinterpret_cast<double*>(base + L.tab);
-  g.mass = reinterpret_cast<double*>(base + L.mass);
-  g.pmass = reinterpret_cast<double*>(base + L.pmass);
-  g.pg = reinterpret_cast<double*>(base + L.pg);
-  g.qb = reinterpret_cast<double*>(base + L.qb);
-  g.ainv = reinterpret_cast<int*>(base + L.ainv);
+  g.tab = L.tab; g.mass = L.mass; g.pmass = L.pmass; g.pg = L.pg; g.qb = L.qb; g.ainv = L.ainv;
   g.loose_hist = std::pow(10.0, -(double)h->ge_loose_hist);
-  g.lo = reinterpret_cast<int*>(base + L.lo);
-  g.wlo = reinterpret_cast<double*>(base + L.wlo);
-  g.slab = reinterpret_cast<double*>(base + L.slab);
-  g.span = reinterpret_cast<int*>(base + L.span);
-  g.ctr = reinterpret_cast<unsigned*>(base + L.ctr);
-  g.gran = reinterpret_cast<unsigned long long*>(base + L.gran);
-  int* d_ids = reinterpret_cast<int*>(base + L.ids);
-  int* d_resume = reinterpret_cast<int*>(base + L.resume);
-  g.cal_ids = d_ids;
-  g.saved = reinterpret_cast<GeState*>(base + L.saved);
-  g.resume = d_resume;
-  g.out_done = reinterpret_cast<int*>(base + L.done);
-  g.err = reinterpret_cast<unsigned*>(base + L.err);
+  g.lo = L.lo; g.wlo = L.wlo; g.slab = L.slab; g.span = L.span; g.ctr = L.ctr; g.gran = L.gran;
+  int *d_ids = L.ids, *d_resume = L.resume, *outi = L.outi;
+  g.cal_ids = d_ids; g.saved = L.saved; g.resume = d_resume; g.out_done = L.done;
+  g.err = L.err;
   g.done_ctr = g.err + 1;
-  double* outd = reinterpret_cast<double*>(base + L.outd);
-  int* outi = reinterpret_cast<int*>(base + L.outi);
+  double* outd = L.outd;
   g.out_r = outd; g.out_K = outd + n_cal; g.out_Ks = outd + 2 * n_cal;
   g.out_steps = outi; g.out_cyc = outi + n_cal; g.out_its = outi + 2 * n_cal; g.out_status = outi + 3 * n_cal;
-  g.out_prof = reinterpret_cast<double*>(base + L.prof);
-  g.out_evlog = reinterpret_cast<double*>(base + L.evlog);
+  g.out_prof = L.prof; g.out_evlog = L.evlog;
   AIY_HIP(h, hipMemsetAsync(g.out_evlog, 0, (size_t)n_cal * kGeEvLog * kGeEvRec * sizeof(double), st));
-  AIY_HIP(h, hipMemcpyAsync(base + L.cal, cals.data(), sizeof(GeCalDev) * n_cal, hipMemcpyHostToDevice, st));
+  AIY_HIP(h, hipMemcpyAsync(L.cal, cals.data(), sizeof(GeCalDev) * n_cal, hipMemcpyHostToDevice, st));
   AIY_HIP(h, hipMemsetAsync(d_resume, 0, (size_t)n_cal * sizeof(int), st));
   AIY_HIP(h, hipMemsetAsync(g.out_done, 0, (size_t)n_cal * sizeof(int), st));
-  for (hipEvent_t& e : h->ge_ev)
-    if (!e) AIY_HIP(h, hipEventCreate(&e));
+  AIY_HIP(h, h->ge_timer.ensure());
   std::vector<int> active(n_cal), done(n_cal, 0), resume(n_cal, 0);
   for (int c = 0; c < n_cal; ++c) active[c] = c;
   h->ge_rounds = 0;
@@ -1172,16 +1141,11 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
     const int n = (int)active.size();
     GePlan p;
     if (!ge_make_plan(h, n, S, n_a, p)) return fail(h, AIY_ERR_STATE, "device-resident GE: no plan for %d calibrations", n);
-    if (hipFuncSetAttribute(p.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess) {
-      (void)hipGetLastError();
+    const Admit adm = admit_launch(p.fn, p.th, p.lds, true);
+    if (adm != Admit::fits) {
       if (h->ge_rounds == 0) return 0;
-      return fail(h, AIY_ERR_STATE, "device-resident GE: dynamic LDS attribute");
-    }
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p.fn, p.th, p.lds) != hipSuccess || per_cu < 1) {
-      (void)hipGetLastError();
-      if (h->ge_rounds == 0) return 0;
-      return fail(h, AIY_ERR_STATE, "device-resident GE: occupancy query");
+      return fail(h, AIY_ERR_STATE, adm == Admit::attr_error ? "device-resident GE: dynamic LDS attribute"
+                                                             : "device-resident GE: occupancy query");
     }
     g.G = p.G; g.nj = p.nj; g.cap = p.cap; g.n_work = n * p.G;
     g.stop_at = (h->ge_rebalance > 0 && n > 4) ? std::max(1, (n * h->ge_rebalance + 99) / 100) : 0;
@@ -1193,18 +1157,14 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
     AIY_HIP(h, hipMemsetAsync(g.gran, 0, (size_t)n * 2 * p.G * kHcRedRec * sizeof(unsigned long long), st));
     AIY_HIP(h, hipMemsetAsync(g.err, 0, 256, st));
     void* args[] = {&g};
-    AIY_HIP(h, hipEventRecord(h->ge_ev[0], st));
+    AIY_HIP(h, h->ge_timer.begin(st));
     AIY_HIP(h, hipLaunchKernel(p.fn, dim3(p.blocks), dim3(p.th), args, p.lds, st));
-    AIY_HIP(h, hipEventRecord(h->ge_ev[1], st));
+    AIY_HIP(h, h->ge_timer.end(st));
     unsigned errw[3] = {0, 0, 0};   // error, finished clusters, clusters stopped inside a solve
     AIY_HIP(h, hipMemcpyAsync(errw, g.err, sizeof(errw), hipMemcpyDeviceToHost, st));
     AIY_HIP(h, hipMemcpyAsync(done.data(), g.out_done, sizeof(int) * n_cal, hipMemcpyDeviceToHost, st));
     AIY_HIP(h, hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ge_ev[0], h->ge_ev[1]) == hipSuccess) {
-      h->ge_ms_sum += ms;
-      h->ge_launches += 1;
-    }
+    h->ge_timer.collect();
     ++h->ge_rounds;
     h->ge_mid_stops += errw[2];
     const unsigned err = errw[0];
@@ -1282,13 +1242,10 @@ extern "C" int32_t aiy_ge_last_rounds(aiy_handle* h, int32_t* launches, int32_t*
 extern "C" int32_t aiy_ge_launch_stats(aiy_handle* h, double* ms_sum, int64_t* launches, double* point_matvecs,
                                        double* egm_cycles, int32_t reset) {
   if (!h) return AIY_ERR_ARG;
-  if (ms_sum) *ms_sum = h->ge_ms_sum;
-  if (launches) *launches = h->ge_launches;
+  h->ge_timer.read(ms_sum, launches, reset != 0);
   if (point_matvecs) *point_matvecs = h->ge_points;
   if (egm_cycles) *egm_cycles = h->ge_egm_cycles;
   if (reset) {
-    h->ge_ms_sum = 0.0;
-    h->ge_launches = 0;
     h->ge_points = 0.0;
     h->ge_egm_cycles = 0.0;
   }

@@ -328,28 +328,29 @@ __global__ void hist_K_sum_kernel(int n_cal, const double* __restrict__ part, do
   for (int b = 0; b < kKBlocks; ++b) k += part[(size_t)cal * kKBlocks + b];
   K[cal] = k;
 }
-// K of every calibration into h->d_K[0, n_cal) (partials behind it)
-static void launch_hist_K(aiy_handle* h, int n_cal, int S, int n_a, const double* mass, const double* a_grid,
+// K of every calibration into d_K[0, n_cal) (partials behind it)
+static void launch_hist_K(double* d_K, int n_cal, int S, int n_a, const double* mass, const double* a_grid,
                           hipStream_t st) {
-  double* part = h->d_K + n_cal;
+  double* part = d_K + n_cal;
   hipLaunchKernelGGL(hist_K_kernel, dim3(kKBlocks, n_cal), dim3(kKThreads), 0, st, S, n_a, mass, a_grid, part);
-  hipLaunchKernelGGL(hist_K_sum_kernel, dim3((n_cal + 63) / 64), dim3(64), 0, st, n_cal, (const double*)part, h->d_K);
+  hipLaunchKernelGGL(hist_K_sum_kernel, dim3((n_cal + 63) / 64), dim3(64), 0, st, n_cal, (const double*)part, d_K);
 }
 
-static int32_t ensure_hist_scratch(aiy_handle* h, int n_cal) {
-  if ((size_t)n_cal <= h->hist_cap) return AIY_OK;
-  if (h->d_hdist) { (void)hipFree(h->d_hdist); (void)hipFree(h->d_K); (void)hipFree(h->d_hlast); }
-  if (h->h_hdist) { (void)hipHostFree(h->h_hdist); (void)hipHostFree(h->h_K); (void)hipHostFree(h->h_hlast); }
-  h->d_hdist = nullptr; h->d_K = nullptr; h->d_hlast = nullptr;
-  h->h_hdist = nullptr; h->h_K = nullptr; h->h_hlast = nullptr; h->hist_cap = 0;
-  AIY_HIP(h, hipMalloc((void**)&h->d_hdist, sizeof(unsigned long long) * kSlots * n_cal));
-  AIY_HIP(h, hipMalloc((void**)&h->d_K, sizeof(double) * n_cal * (1 + kKBlocks)));   // K, then partials
-  AIY_HIP(h, hipMalloc((void**)&h->d_hlast, sizeof(int) * (n_cal + 1)));   // + monotone flag
-  AIY_HIP(h, hipHostMalloc((void**)&h->h_hdist, sizeof(unsigned long long) * kSlots * n_cal, hipHostMallocDefault));
-  AIY_HIP(h, hipHostMalloc((void**)&h->h_K, sizeof(double) * n_cal, hipHostMallocDefault));
-  AIY_HIP(h, hipHostMalloc((void**)&h->h_hlast, sizeof(int) * (n_cal + 1), hipHostMallocDefault));
-  h->hist_cap = n_cal;
-  return AIY_OK;
+// Convergence slots of a solve, on the device (k_per = 1 + kKBlocks: K, then its partials)
+// and in the pinned host mirror (k_per = 1).
+struct HistSlots {
+  unsigned long long* dist;   // [n_cal][kSlots]
+  double* K;                  // [k_per][n_cal]
+  int* last;                  // [n_cal] + monotone flag
+  size_t bytes;
+};
+static HistSlots hist_slots(Carve c, int n_cal, int k_per) {
+  HistSlots L;
+  L.dist = c.take<unsigned long long>((size_t)kSlots * n_cal);
+  L.K = c.take<double>((size_t)n_cal * k_per);
+  L.last = c.take<int>((size_t)n_cal + 1);
+  L.bytes = c.bytes();
+  return L;
 }
 
 }  // namespace aiy
@@ -380,34 +381,36 @@ extern "C" int32_t aiy_hist_solve(aiy_handle* h, int32_t n_cal, int32_t S, int32
   if (max_iter < 1) return fail(h, AIY_ERR_ARG, "max_iter must be >= 1");
   if (chunk <= 0) chunk = 64;
   AIY_HIP(h, hipSetDevice(h->device));
-  int32_t rc = ensure_hist_scratch(h, n_cal);
+  int32_t rc = h->hist_dev.reserve(h, hist_slots(Carve(), n_cal, 1 + kKBlocks).bytes);
+  if (rc == AIY_OK) rc = h->hist_pin.reserve(h, hist_slots(Carve(), n_cal, 1).bytes);
   if (rc) return rc;
+  const HistSlots dv = hist_slots(Carve(h->hist_dev.get()), n_cal, 1 + kKBlocks);
+  const HistSlots hv = hist_slots(Carve(h->hist_pin.get()), n_cal, 1);
   hipStream_t st = as_stream(stream);
   AIY_USE_STREAM(h, st);
   const size_t per = (size_t)n_cal * S * n_a;
   double* T = work;          // [n_cal][S][n_a] push accumulator (kept zero between iterations)
   double* alt = work + per;  // [n_cal][S][n_a] ping-pong partner of `mass`
-  AIY_HIP(h, hipMemsetAsync(h->d_hdist, 0, sizeof(unsigned long long) * kSlots * n_cal, st));
-  AIY_HIP(h, hipMemsetAsync(h->d_hlast, 0, sizeof(int) * (n_cal + 1), st));
+  AIY_HIP(h, hipMemsetAsync(dv.dist, 0, sizeof(unsigned long long) * kSlots * n_cal, st));
+  AIY_HIP(h, hipMemsetAsync(dv.last, 0, sizeof(int) * (n_cal + 1), st));
   if (h->hist_resident && !h->hist_fused) {
     // the whole iteration in one device-resident launch (hist_resident.hip)
-    for (hipEvent_t& e : h->hc_ev)
-      if (!e) AIY_HIP(h, hipEventCreate(&e));
-    rc = hist_solve_resident(h, n_cal, S, n_a, lo, wlo, P, tol, max_iter, mass, h->d_hlast, st);
+    AIY_HIP(h, h->hc_timer.ensure());
+    rc = hist_solve_resident(h, n_cal, S, n_a, lo, wlo, P, tol, max_iter, mass, dv.last, st);
     if (rc == AIY_OK) {
-      launch_hist_K(h, n_cal, S, n_a, mass, a_grid, st);
+      launch_hist_K(dv.K, n_cal, S, n_a, mass, a_grid, st);
       AIY_CHECK_LAUNCH(h);
-      AIY_HIP(h, hipMemcpyAsync(h->h_hlast, h->d_hlast, sizeof(int) * n_cal, hipMemcpyDeviceToHost, st));
-      AIY_HIP(h, hipMemcpyAsync(h->h_K, h->d_K, sizeof(double) * n_cal, hipMemcpyDeviceToHost, st));
+      AIY_HIP(h, hipMemcpyAsync(hv.last, dv.last, sizeof(int) * n_cal, hipMemcpyDeviceToHost, st));
+      AIY_HIP(h, hipMemcpyAsync(hv.K, dv.K, sizeof(double) * n_cal, hipMemcpyDeviceToHost, st));
       AIY_HIP(h, hipStreamSynchronize(st));
       for (int c = 0; c < n_cal; ++c) {
-        iters_out[c] = h->h_hlast[c];
-        K_out[c] = h->h_K[c];
+        iters_out[c] = hv.last[c];
+        K_out[c] = hv.K[c];
       }
       return AIY_OK;
     }
     if (rc != AIY_ERR_UNSUPPORTED) return rc;
-    AIY_HIP(h, hipMemsetAsync(h->d_hlast, 0, sizeof(int) * (n_cal + 1), st));   // push/mix below
+    AIY_HIP(h, hipMemsetAsync(dv.last, 0, sizeof(int) * (n_cal + 1), st));   // push/mix below
   }
   // Fused path: the tile source ranges jb [n_cal][S][n_a + 1] (int) live in T's space.
   int* jb = reinterpret_cast<int*>(T);
@@ -415,11 +418,11 @@ extern "C" int32_t aiy_hist_solve(aiy_handle* h, int32_t n_cal, int32_t S, int32
   bool fused = h->hist_fused && step_lds <= 128 * 1024;
   if (fused) {
     hipLaunchKernelGGL(hist_range_kernel, dim3((n_a + 1 + 255) / 256, S, n_cal), dim3(256), 0, st, S, n_a, lo, jb,
-                       h->d_hlast + n_cal);
+                       dv.last + n_cal);
     AIY_CHECK_LAUNCH(h);
-    AIY_HIP(h, hipMemcpyAsync(h->h_hlast + n_cal, h->d_hlast + n_cal, sizeof(int), hipMemcpyDeviceToHost, st));
+    AIY_HIP(h, hipMemcpyAsync(hv.last + n_cal, dv.last + n_cal, sizeof(int), hipMemcpyDeviceToHost, st));
     AIY_HIP(h, hipStreamSynchronize(st));
-    fused = h->h_hlast[n_cal] == 0;   // every row monotone
+    fused = hv.last[n_cal] == 0;   // every row monotone
   }
   if (!fused) AIY_HIP(h, hipMemsetAsync(T, 0, per * sizeof(double), st));
   auto step_fn = S <= 8 ? (const void*)hist_step_kernel<8>
@@ -438,29 +441,29 @@ extern "C" int32_t aiy_hist_solve(aiy_handle* h, int32_t n_cal, int32_t S, int32
       double* dst = (k & 1) ? alt : mass;
       if (fused) {
         void* args[] = {(void*)&S, (void*)&n_a, (void*)&lo, (void*)&wlo, (void*)&jb, (void*)&P, (void*)&src,
-                        (void*)&dst, (void*)&h->d_hdist, (void*)&h->d_hlast, (void*)&k, (void*)&tol};
+                        (void*)&dst, (void*)&dv.dist, (void*)&dv.last, (void*)&k, (void*)&tol};
         AIY_HIP(h, hipLaunchKernel(step_fn, gstep, dim3(256), args, step_lds, st));
         continue;
       }
-      hipLaunchKernelGGL(hist_push_kernel, gpush, dim3(256), 0, st, S, n_a, lo, wlo, src, T, h->d_hdist, k, tol);
+      hipLaunchKernelGGL(hist_push_kernel, gpush, dim3(256), 0, st, S, n_a, lo, wlo, src, T, dv.dist, k, tol);
       if (S <= 8)
-        hipLaunchKernelGGL(hist_mix_kernel<8>, gmix, dim3(256), 0, st, S, n_a, P, T, src, dst, h->d_hdist, h->d_hlast, k, tol);
+        hipLaunchKernelGGL(hist_mix_kernel<8>, gmix, dim3(256), 0, st, S, n_a, P, T, src, dst, dv.dist, dv.last, k, tol);
       else if (S <= 16)
-        hipLaunchKernelGGL(hist_mix_kernel<16>, gmix, dim3(256), 0, st, S, n_a, P, T, src, dst, h->d_hdist, h->d_hlast, k, tol);
+        hipLaunchKernelGGL(hist_mix_kernel<16>, gmix, dim3(256), 0, st, S, n_a, P, T, src, dst, dv.dist, dv.last, k, tol);
       else if (S <= 32)
-        hipLaunchKernelGGL(hist_mix_kernel<32>, gmix, dim3(256), 0, st, S, n_a, P, T, src, dst, h->d_hdist, h->d_hlast, k, tol);
+        hipLaunchKernelGGL(hist_mix_kernel<32>, gmix, dim3(256), 0, st, S, n_a, P, T, src, dst, dv.dist, dv.last, k, tol);
       else
-        hipLaunchKernelGGL(hist_mix_kernel<64>, gmix, dim3(256), 0, st, S, n_a, P, T, src, dst, h->d_hdist, h->d_hlast, k, tol);
+        hipLaunchKernelGGL(hist_mix_kernel<64>, gmix, dim3(256), 0, st, S, n_a, P, T, src, dst, dv.dist, dv.last, k, tol);
     }
     AIY_CHECK_LAUNCH(h);
-    AIY_HIP(h, hipMemcpyAsync(h->h_hlast, h->d_hlast, sizeof(int) * n_cal, hipMemcpyDeviceToHost, st));
-    AIY_HIP(h, hipMemcpyAsync(h->h_hdist, h->d_hdist, sizeof(unsigned long long) * kSlots * n_cal, hipMemcpyDeviceToHost, st));
+    AIY_HIP(h, hipMemcpyAsync(hv.last, dv.last, sizeof(int) * n_cal, hipMemcpyDeviceToHost, st));
+    AIY_HIP(h, hipMemcpyAsync(hv.dist, dv.dist, sizeof(unsigned long long) * kSlots * n_cal, hipMemcpyDeviceToHost, st));
     AIY_HIP(h, hipStreamSynchronize(st));
     bool all = true;
     for (int c = 0; c < n_cal; ++c) {
-      const int last = h->h_hlast[c];
+      const int last = hv.last[c];
       double d;
-      unsigned long long b = h->h_hdist[c * kSlots + last % 3];
+      unsigned long long b = hv.dist[c * kSlots + last % 3];
       std::memcpy(&d, &b, sizeof(d));
       all = all && ((last >= 1 && !(d >= tol)) || last >= max_iter);
     }
@@ -469,28 +472,23 @@ extern "C" int32_t aiy_hist_solve(aiy_handle* h, int32_t n_cal, int32_t S, int32
   }
   // bring every calibration's final distribution into `mass`
   for (int c = 0; c < n_cal; ++c) {
-    const int last = h->h_hlast[c];
+    const int last = hv.last[c];
     iters_out[c] = last;
     if (last & 1) {
       const size_t off = (size_t)c * S * n_a;
       AIY_HIP(h, hipMemcpyAsync(mass + off, alt + off, (size_t)S * n_a * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
   }
-  launch_hist_K(h, n_cal, S, n_a, mass, a_grid, st);
+  launch_hist_K(dv.K, n_cal, S, n_a, mass, a_grid, st);
   AIY_CHECK_LAUNCH(h);
-  AIY_HIP(h, hipMemcpyAsync(h->h_K, h->d_K, sizeof(double) * n_cal, hipMemcpyDeviceToHost, st));
+  AIY_HIP(h, hipMemcpyAsync(hv.K, dv.K, sizeof(double) * n_cal, hipMemcpyDeviceToHost, st));
   AIY_HIP(h, hipStreamSynchronize(st));
-  for (int c = 0; c < n_cal; ++c) K_out[c] = h->h_K[c];
+  for (int c = 0; c < n_cal; ++c) K_out[c] = hv.K[c];
   return AIY_OK;
 }
 
 extern "C" int32_t aiy_hist_launch_stats(aiy_handle* h, double* ms_sum, int64_t* launches, int32_t reset) {
   if (!h) return AIY_ERR_ARG;
-  if (ms_sum) *ms_sum = h->hc_ms_sum;
-  if (launches) *launches = h->hc_launches;
-  if (reset) {
-    h->hc_ms_sum = 0.0;
-    h->hc_launches = 0;
-  }
+  h->hc_timer.read(ms_sum, launches, reset != 0);
   return AIY_OK;
 }

@@ -7,7 +7,10 @@
 // prefix / suffix search.
 #pragma once
 
+#include <algorithm>
+
 #include "common.h"
+#include "hist_scratch.h"
 
 namespace aiy {
 
@@ -21,8 +24,6 @@ struct HcGather {
 };
 constexpr size_t kHcLdsTotal = 160 * 1024;         // per CU
 constexpr unsigned long long kHcTimeoutTicks = 200000000ull;   // 2 s of the 100 MHz clock
-constexpr int kHcCtrStride = 32;                   // uints between cluster counters (128 B)
-constexpr int kHcRedRec = 16;                      // 8-byte words per (parity, workgroup) record of `dist`
 constexpr int kHcRed = 8;                          // values per cluster reduction (at most)
 static_assert(2 * kHcRed <= kHcRedRec, "two granules per value of a reduction");
 
@@ -300,5 +301,35 @@ constexpr int kHpTH = AIY_HP_TH;   // tuning builds only
 #else
 constexpr int kHpTH = 512;
 #endif
+
+// ---- host side of a resident cluster launch ----
+// LDS of one CU as the resident kernel `fn` may use it: the total (the device's, at most
+// kHcLdsTotal), the kernel's static part and the dynamic budget left (a multiple of 256,
+// 1 KB kept free).  False when a query fails or the static part leaves under 4 KB.
+struct HcLds { size_t total, stat, dyn; };
+inline bool hc_lds_budget(int device, const void* fn, HcLds& b) {
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return false;
+  int lds_dev = 0;
+  if (hipDeviceGetAttribute(&lds_dev, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) != hipSuccess)
+    return false;
+  b.total = std::min<size_t>(kHcLdsTotal, (size_t)lds_dev);
+  b.stat = fa.sharedSizeBytes;
+  if (b.stat + 4096 >= b.total) return false;
+  b.dyn = (b.total - b.stat - 1024) / 256 * 256;
+  return true;
+}
+
+// Workgroups per calibration cluster and columns per workgroup: as many workgroups as the
+// CUs shared among n_cal clusters allow, within [g_min, min(g_cap, kHcMaxG)], every one
+// owning at least one of the n_a columns.  False when g_min workgroups cannot be had.
+inline bool hc_cluster_split(int n_a, int g_min, int g_cap, int cus, int n_cal, int* G, int* nj) {
+  if (g_min > kHcMaxG || g_min > cus) return false;
+  int g = std::max(g_min, std::min(std::min(g_cap, kHcMaxG), cus / std::max(1, n_cal)));
+  g = std::min(g, n_a);
+  *nj = (n_a + g - 1) / g;
+  *G = (n_a + *nj - 1) / *nj;
+  return true;
+}
 
 }  // namespace aiy

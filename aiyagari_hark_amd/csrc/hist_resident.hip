@@ -539,6 +539,7 @@ static bool hc_make_plan(aiy_handle* h, int n_cal, int S, int n_a, HcPlan& p, bo
   if (S < 1 || n_a < 2 || S > (krylov ? 64 : 32)) return false;
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) return false;
+  HcLds lds;
   if (krylov && S > 8) {   // pull form (hist_pull.h): vectors in HBM, every calibration at once
     p.pull = true;
     p.smax = 32;
@@ -547,26 +548,14 @@ static bool hc_make_plan(aiy_handle* h, int n_cal, int S, int n_a, HcPlan& p, bo
     p.cap = 0;
     p.vblock = 0;
     p.fn = hist_pull_pick(S);
-    if (!p.fn) return false;
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, p.fn) != hipSuccess) return false;
-    int lds_dev = 0;
-    if (hipDeviceGetAttribute(&lds_dev, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device) != hipSuccess)
-      return false;
-    const size_t lds_total = std::min<size_t>(kHcLdsTotal, (size_t)lds_dev);
-    if (fa.sharedSizeBytes + 4096 >= lds_total) return false;
-    const size_t budget = lds_total - fa.sharedSizeBytes - 1024;
+    if (!p.fn || !hc_lds_budget(h->device, p.fn, lds)) return false;
+    const size_t budget = lds.total - lds.stat - 1024;
     // the staged inverse lottery plus room for a 64-column chunk of row sums
     if (budget <= (size_t)S * 64 * sizeof(double)) return false;
     const int max_own = (int)((budget - (size_t)S * 64 * sizeof(double)) / (sizeof(int) * (size_t)S)) - 2;
     if (max_own < 1) return false;
-    const int g_min = (n_a + max_own - 1) / max_own;
-    if (g_min > kHcMaxG || g_min > cus) return false;
     const int g_cap = h->hist_cluster_cap > 0 ? h->hist_cluster_cap : kHcMaxG;
-    int G = std::max(g_min, std::min(std::min(g_cap, kHcMaxG), cus / std::max(1, n_cal)));
-    G = std::min(G, n_a);
-    p.nj = (n_a + G - 1) / G;
-    p.G = (n_a + p.nj - 1) / p.nj;
+    if (!hc_cluster_split(n_a, (n_a + max_own - 1) / max_own, g_cap, cus, n_cal, &p.G, &p.nj)) return false;
     p.cals_per_launch = std::max(1, cus / p.G);
     return hist_pull_plan(S, p.nj, budget, &p.cw, &p.lds);
   }
@@ -574,51 +563,25 @@ static bool hc_make_plan(aiy_handle* h, int n_cal, int S, int n_a, HcPlan& p, bo
   p.smax = S <= 8 ? 8 : (S <= 16 ? 16 : 32);
   const int kc_max = p.smax == 8 ? 2 : 1;
   p.th = 512;
-  const int g_min = (n_a + p.th * kc_max - 1) / (p.th * kc_max);
-  if (g_min > kHcMaxG || g_min > cus) return false;
   const int g_cap = h->hist_cluster_cap > 0 ? h->hist_cluster_cap : 32;
-  int G = std::max(g_min, std::min(std::min(g_cap, kHcMaxG), cus / std::max(1, n_cal)));
-  G = std::min(G, n_a);
-  p.nj = (n_a + G - 1) / G;
-  p.G = (n_a + p.nj - 1) / p.nj;                    // every workgroup owns >= 1 column
+  // every workgroup owns >= 1 column
+  if (!hc_cluster_split(n_a, (n_a + p.th * kc_max - 1) / (p.th * kc_max), g_cap, cus, n_cal, &p.G, &p.nj)) return false;
   p.kc = p.nj <= p.th ? 1 : 2;
   if (p.kc > kc_max) return false;
   p.cals_per_launch = std::max(1, cus / p.G);
   int smax_k = p.smax;
   p.fn = krylov ? hist_bicg_pick(S, p.smax, p.kc, &smax_k, h->hist_pull != 0) : hc_pick(p.smax, p.kc);
   p.pull_small = krylov && h->hist_pull != 0 && p.smax == 8;
-  if (!p.fn) return false;
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, p.fn) != hipSuccess) return false;
-  const size_t stat = fa.sharedSizeBytes;
   // the LDS budget is the device's own (160 KB per CU on gfx950; an arch override with
-  // less LDS makes the plan not fit instead of failing the attribute call below)
-  int lds_dev = 0;
-  if (hipDeviceGetAttribute(&lds_dev, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device) != hipSuccess)
-    return false;
-  const size_t lds_total = std::min<size_t>(kHcLdsTotal, (size_t)lds_dev);
-  if (stat + 4096 >= lds_total) return false;
-  p.lds = (lds_total - stat - 1024) / 256 * 256;
+  // less LDS makes the plan not fit instead of failing the attribute call of the launch)
+  if (!p.fn || !hc_lds_budget(h->device, p.fn, lds)) return false;
+  p.lds = lds.dyn;
   // BiCGSTAB: one resident vector (v, [KC][SMAX][TH] doubles) behind the span buffer
   const size_t vbytes = krylov && smax_k <= 8 ? (size_t)p.kc * smax_k * p.th * sizeof(double) : 0;
   p.vblock = krylov && smax_k > 8 ? (size_t)p.kc * smax_k * p.th : 0;   // v in HBM, doubles per workgroup
   if (p.lds <= vbytes + 4096) return false;
   p.cap = (int)((p.lds - vbytes) / sizeof(double));
   return true;
-}
-
-static int32_t hc_scratch(aiy_handle* h, int cals, int G, int cap) {
-  const size_t need = (size_t)cals * G * 2 * cap * sizeof(double) + (size_t)cals * G * 32 * 4 * sizeof(int) +
-                      (size_t)cals * kHcCtrStride * sizeof(unsigned) + (size_t)cals * 2 * G * kHcRedRec * sizeof(double) +
-                      256;
-  if (need > h->hc_cap) {
-    if (h->d_hc) (void)hipFree(h->d_hc);
-    h->d_hc = nullptr;
-    h->hc_cap = 0;
-    AIY_HIP(h, hipMalloc(&h->d_hc, need));
-    h->hc_cap = need;
-  }
-  return AIY_OK;
 }
 
 // A whole distribution iteration of n_cal calibrations in cluster launches.  Returns
@@ -632,84 +595,48 @@ int32_t hist_solve_resident(aiy_handle* h, int n_cal, int S, int n_a, const int*
   if (!hc_make_plan(h, n_cal, S, n_a, p, krylov)) return AIY_ERR_UNSUPPORTED;
   // a launch shape the device does not admit is "unsupported" (the caller's push/mix
   // fallback runs), not a hard error
-  if (hipFuncSetAttribute(p.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return AIY_ERR_UNSUPPORTED;
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p.fn, p.th, p.lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return AIY_ERR_UNSUPPORTED;
-  }
-  if (per_cu < 1) return AIY_ERR_UNSUPPORTED;
+  if (admit_launch(p.fn, p.th, p.lds, true) != Admit::fits) return AIY_ERR_UNSUPPORTED;
   const int per_launch = std::min(n_cal, p.cals_per_launch);
-  int32_t rc = hc_scratch(h, per_launch, p.G, p.cap);
+  int32_t rc = h->hc.reserve(h, hc_scratch(Carve(), per_launch, p.G, p.cap).bytes);
   if (rc) return rc;
-  char* base = static_cast<char*>(h->d_hc);
+  const HcScratch L = hc_scratch(Carve(h->hc.get()), per_launch, p.G, p.cap);
   HcRun r;
   r.n_cal = n_cal; r.S = S; r.n_a = n_a; r.G = p.G; r.nj = p.nj; r.cap = p.cap; r.cw = p.cw;
   r.lo = lo; r.wlo = wlo; r.P = P; r.mass = mass; r.iters_out = d_iters; r.tol = tol; r.max_iter = max_iter;
   r.tolv = krylov ? h->hist_tolv : nullptr;   // per-calibration tolerances (BiCGSTAB form)
-  r.slab = reinterpret_cast<double*>(base);
-  size_t off = (size_t)per_launch * p.G * 2 * p.cap * sizeof(double);
-  r.span = reinterpret_cast<int*>(base + off);
-  off += (size_t)per_launch * p.G * 32 * 4 * sizeof(int);
-  r.ctr = reinterpret_cast<unsigned*>(base + off);
-  const size_t ctr_bytes = (size_t)per_launch * kHcCtrStride * sizeof(unsigned);
-  off += ctr_bytes;
-  r.dist = reinterpret_cast<double*>(base + off);
-  off += (size_t)per_launch * 2 * p.G * kHcRedRec * sizeof(double);
+  r.slab = L.slab; r.span = L.span; r.ctr = L.ctr; r.dist = L.dist; r.err = L.err;
   r.accel = krylov ? 0 : h->hist_accel;
   r.dbuf = nullptr;
   r.ainv = nullptr;
-  if (p.pull) {   // pull form: four [S][n_a] vectors per calibration + the inverse lottery
-    const size_t vb = (size_t)n_cal * 4 * S * n_a * sizeof(double);
-    const size_t db = vb + (size_t)n_cal * S * (n_a + 1) * sizeof(int);
-    if (db > h->hc_dcap) {
-      if (h->d_hcd) (void)hipFree(h->d_hcd);
-      h->d_hcd = nullptr;
-      h->hc_dcap = 0;
-      AIY_HIP(h, hipMalloc(&h->d_hcd, db));
-      h->hc_dcap = db;
-    }
-    r.dbuf = static_cast<double*>(h->d_hcd);
-    r.ainv = reinterpret_cast<int*>(static_cast<char*>(h->d_hcd) + vb);
-  } else if (r.accel > 0 || krylov) {   // Aitken: stored differences; BiCGSTAB: the p scratch rows
+  if (p.pull || r.accel > 0 || krylov) {
     if (r.accel > 0 && r.accel < 4) r.accel = 4;
-    // p rows (+ v blocks); pull form: + the matvec input rows and the inverse lottery
-    const size_t dvec = ((size_t)n_cal * S * n_a * (p.pull_small ? 2 : 1) + (size_t)per_launch * p.G * p.vblock) *
-                        sizeof(double);
-    const size_t db = dvec + (p.pull_small ? (size_t)n_cal * S * (n_a + 1) * sizeof(int) : 0);
-    if (db > h->hc_dcap) {
-      if (h->d_hcd) (void)hipFree(h->d_hcd);
-      h->d_hcd = nullptr;
-      h->hc_dcap = 0;
-      AIY_HIP(h, hipMalloc(&h->d_hcd, db));
-      h->hc_dcap = db;
-    }
-    r.dbuf = static_cast<double*>(h->d_hcd);
-    if (p.pull_small) r.ainv = reinterpret_cast<int*>(static_cast<char*>(h->d_hcd) + dvec);
+    const size_t pts = (size_t)n_cal * S * n_a;
+    // pull form: four [S][n_a] vectors per calibration; Aitken: stored differences; BiCGSTAB:
+    // the p rows (+ v blocks; small pull form: + the matvec input rows); both pull forms:
+    // + the inverse lottery
+    const size_t vec = p.pull ? 4 * pts : pts * (p.pull_small ? 2 : 1) + (size_t)per_launch * p.G * p.vblock;
+    const size_t ainv = p.pull || p.pull_small ? (size_t)n_cal * S * (n_a + 1) : 0;
+    rc = h->hcd.reserve(h, hcd_scratch(Carve(), vec, ainv).bytes);
+    if (rc) return rc;
+    const HcdScratch D = hcd_scratch(Carve(h->hcd.get()), vec, ainv);
+    r.dbuf = D.vec;
+    if (ainv) r.ainv = D.ainv;
   }
-  r.err = reinterpret_cast<unsigned*>(base + off);
   for (int c0 = 0; c0 < n_cal; c0 += per_launch) {
     const int nc = std::min(per_launch, n_cal - c0);
     r.cal0 = c0;
-    AIY_HIP(h, hipMemsetAsync(r.ctr, 0, ctr_bytes, st));
+    AIY_HIP(h, hipMemsetAsync(r.ctr, 0, L.ctr_bytes, st));
     if (krylov)   // reduction granules: epochs count from 1 in every launch
-      AIY_HIP(h, hipMemsetAsync(r.dist, 0, (size_t)per_launch * 2 * p.G * kHcRedRec * sizeof(double), st));
+      AIY_HIP(h, hipMemsetAsync(r.dist, 0, L.dist_bytes, st));
     AIY_HIP(h, hipMemsetAsync(r.err, 0, sizeof(unsigned), st));
     void* args[] = {&r};
-    AIY_HIP(h, hipEventRecord(h->hc_ev[0], st));
+    AIY_HIP(h, h->hc_timer.begin(st));
     AIY_HIP(h, hipLaunchKernel(p.fn, dim3(nc * p.G), dim3(p.th), args, p.lds, st));
-    AIY_HIP(h, hipEventRecord(h->hc_ev[1], st));
+    AIY_HIP(h, h->hc_timer.end(st));
     unsigned err = 0;
     AIY_HIP(h, hipMemcpyAsync(&err, r.err, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     AIY_HIP(h, hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->hc_ev[0], h->hc_ev[1]) == hipSuccess) {
-      h->hc_ms_sum += ms;
-      h->hc_launches += 1;
-    }
+    h->hc_timer.collect();
     if (err == 2u || err == 3u) return AIY_ERR_UNSUPPORTED;
     if (err) return fail(h, AIY_ERR_STATE, "resident histogram: cluster barrier timed out (workgroups not co-resident?)");
   }

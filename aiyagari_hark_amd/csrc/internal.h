@@ -11,34 +11,28 @@
 #include <vector>
 
 #include "../../include/aiyagari.h"
+#include "carve.h"
+#include "owned.h"
 
+// Every allocation and event of the handle is an owning type of owned.h, grown by reserve()
+// where it is used; a buffer of several arrays is carved by its user's layout function (carve.h).
 struct aiy_handle {
   int device = 0;
   std::string err;
-  // EGM convergence bookkeeping: [n_cal][3] distance slots (bit patterns of
-  // non-negative doubles, atomicMax) and [n_cal] last completed cycle.
-  unsigned long long* d_dist = nullptr;
-  int* d_last = nullptr;
-  size_t egm_cap = 0;
-  int* d_egm_hint = nullptr;         // EGM row hints [work item][rows x S] (egm.hip)
-  double* d_egm_aa = nullptr;        // Anderson mixing of the host-driven EGM solve (egm.hip): the c
-  size_t egm_aa_cap = 0;             //   tables of the last 5 cycles + Gram partials + gamma (doubles)
-  size_t egm_hint_cap = 0;           // ints
+  // EGM convergence bookkeeping (egm.hip, EgmSlots): distance slots (bit patterns of non-negative
+  // doubles, atomicMax), extrapolation factors, last completed cycle; device + pinned host mirror
+  aiy::DeviceBuffer egm_dev; aiy::PinnedBuffer egm_pin;
+  aiy::DeviceBuffer egm_hint;        // EGM row hints [work item][rows x S] ints (egm.hip)
   unsigned long long egm_hint_sig = ~0ull;   // shape the hints belong to
-  // host pinned mirrors
-  unsigned long long* h_dist = nullptr;
-  int* h_last = nullptr;
-  // panel: per-block partial sums
-  double* d_partials = nullptr;
-  unsigned* d_ticket = nullptr;      // last-block-done counter of the period kernel
-  size_t partials_cap = 0;
+  aiy::DeviceBuffer egm_aa;          // Anderson mixing of the host-driven EGM solve (egm.hip): the c
+                                     //   tables of the last 5 cycles + Gram partials + gamma (doubles)
+  // panel: per-block partial sums and the last-block-done counter of the period kernel
+  aiy::DeviceBuffer partials, ticket;
   hipStream_t cap_stream = nullptr;  // hipGraph capture stream
   bool use_graphs = true;
-  // histogram: per-calibration sup-norm slots [n_cal][3] + sums of K
-  unsigned long long* d_hdist = nullptr;
-  double* d_K = nullptr;
-  int* d_hlast = nullptr;
-  size_t hist_cap = 0;
+  // histogram (hist.hip, HistSlots): per-calibration sup-norm slots [n_cal][3], sums of K
+  // (+ partials), last iteration (+ monotone flag); device and pinned host mirror
+  aiy::DeviceBuffer hist_dev; aiy::PinnedBuffer hist_pin;
   bool hist_fused = false;           // AIY_OPT_HIST_FUSED
   bool hist_resident = true;         // AIY_OPT_HIST_RESIDENT (hist_resident.hip)
   int hist_cluster_cap = 0;          // AIY_OPT_HIST_CLUSTER: max workgroups per calibration (0: 32)
@@ -53,13 +47,10 @@ struct aiy_handle {
   const double* egm_tolh = nullptr;
   const double* hist_tolv = nullptr;
   int egm_extrap = 0;                // aiy_ge_stationary: extrapolate the EGM iterates (egm.hip)
-  void* d_hcd = nullptr;             // resident histogram: stored differences (Aitken)
-  size_t hc_dcap = 0;
-  void* d_hc = nullptr;              // resident histogram: slabs, spans, counters, distances
-  size_t hc_cap = 0;
-  hipEvent_t hc_ev[2] = {nullptr, nullptr};
-  double hc_ms_sum = 0.0;
-  long long hc_launches = 0;
+  // resident histogram (hist_resident.hip): hc = slabs, spans, counters, distances (HcScratch);
+  // hcd = stored differences (Aitken) / BiCGSTAB vectors + inverse lottery (HcdScratch)
+  aiy::DeviceBuffer hc, hcd;
+  aiy::LaunchTimer hc_timer;         // aiy_hist_launch_stats
   // device-resident GE search (ge_resident.hip)
   bool ge_resident = false;          // AIY_OPT_GE_RESIDENT
   int cu_limit = 0;                  // AIY_OPT_CU_LIMIT: compute units resident launches may fill (0: all)
@@ -69,36 +60,24 @@ struct aiy_handle {
   int ge_extrap_period = 32;         // AIY_OPT_GE_EXTRAP_PERIOD: EGM cycles between extrapolation checks
   int ge_anderson = 12;              // AIY_OPT_GE_ANDERSON: EGM cycles between Anderson mixes (0: off)
   int ge_logsec = 2;                 // AIY_OPT_GE_LOGSEC: 0 off, 1 two-point log-secant bracketing, 2 also from one point (with loose bracketing)
-  void* d_ge = nullptr;              // tables, masses, lottery, cluster sync of the launch
-  size_t ge_cap = 0;
-  hipEvent_t ge_ev[2] = {nullptr, nullptr};
-  double ge_ms_sum = 0.0, ge_points = 0.0, ge_egm_cycles = 0.0;
-  long long ge_launches = 0;
+  aiy::DeviceBuffer ge;              // tables, masses, lottery, cluster sync of the launch (GeScratch)
+  aiy::LaunchTimer ge_timer;         // aiy_ge_launch_stats
+  double ge_points = 0.0, ge_egm_cycles = 0.0;
   std::vector<double> ge_prof;       // [n_cal][8] per-calibration profile of the last launch
   std::vector<double> ge_evlog;      // [n_cal][32][6] per-evaluation log of the last search
-  // wealth statistics (stats.hip): sort / scan scratch
-  void* d_stats = nullptr;
-  size_t stats_cap = 0;
-  // welfare (welfare.hip): the [n_cal][S] sums of aiy_value_reduce
-  double* d_welf = nullptr;
-  size_t welf_cap = 0;               // doubles
-  unsigned long long* h_hdist = nullptr;
-  double* h_K = nullptr;
-  int* h_hlast = nullptr;
+  aiy::DeviceBuffer stats;           // wealth statistics (stats.hip): sort / scan scratch
+  aiy::DeviceBuffer welf;            // welfare (welfare.hip): the [n_cal][S] sums of aiy_value_reduce
   // resident panel: tagged partial-sum granules + timeout word; option
-  void* d_res_sync = nullptr;
+  aiy::DeviceBuffer res_sync;
   bool use_resident = true;
   int res_shape = 0;                 // resident workgroup shape (AIY_OPT_RESIDENT_SHAPE)
-  hipEvent_t res_ev[2] = {nullptr, nullptr};   // bracket every resident launch (aiy_panel_launch_stats)
-  double res_ms_sum = 0.0;
-  long long res_launches = 0, res_periods = 0;
+  aiy::LaunchTimer res_timer;        // brackets every resident launch (aiy_panel_launch_stats)
+  long long res_periods = 0;
   unsigned res_epoch = 0;            // granule tag base of the next resident launch
   const void* res_occ_fn = nullptr;  // resident shape whose occupancy was last checked
   size_t res_occ_lds = 0;
   // block panel: per-calibration markets + seeds (device + pinned staging)
-  void* d_blk = nullptr;
-  void* h_blk = nullptr;
-  size_t blk_cap = 0;
+  aiy::DeviceBuffer blk_dev; aiy::PinnedBuffer blk_pin;
   bool res_stream = false;           // AIY_OPT_RESIDENT_STREAM
   // RCCL
   ncclComm_t comm = nullptr;
@@ -107,7 +86,7 @@ struct aiy_handle {
   // stream hand-off between calls that share the scratch above (aiy::use_stream)
   hipStream_t last_stream = nullptr;
   bool has_last_stream = false;
-  hipEvent_t hand_ev = nullptr;
+  aiy::Event hand_ev;
 };
 
 // EGM solve loop, cold (m_init == NULL) or warm-started (egm.hip).
@@ -153,9 +132,9 @@ inline hipStream_t as_stream(aiy_stream s) { return reinterpret_cast<hipStream_t
 // already enqueued on the old one, so two streams never interleave on the scratch.
 inline int32_t use_stream(aiy_handle* h, hipStream_t st) {
   if (h->has_last_stream && h->last_stream != st) {
-    if (!h->hand_ev) AIY_HIP(h, hipEventCreateWithFlags(&h->hand_ev, hipEventDisableTiming));
-    if (hipEventRecord(h->hand_ev, h->last_stream) == hipSuccess) {
-      AIY_HIP(h, hipStreamWaitEvent(st, h->hand_ev, 0));
+    AIY_HIP(h, h->hand_ev.ensure(hipEventDisableTiming));
+    if (hipEventRecord(h->hand_ev.get(), h->last_stream) == hipSuccess) {
+      AIY_HIP(h, hipStreamWaitEvent(st, h->hand_ev.get(), 0));
     } else {
       (void)hipGetLastError();   // the old stream is gone: nothing left to order against
     }
@@ -169,6 +148,25 @@ inline int32_t use_stream(aiy_handle* h, hipStream_t st) {
     int32_t _r = aiy::use_stream((h), (st));         \
     if (_r) return _r;                               \
   } while (0)
+
+// Does the device admit a resident launch of `fn` (`threads` per workgroup, `lds` bytes of dynamic
+// LDS, at least one workgroup per CU)?  set_attr: first raise the kernel's dynamic-LDS limit to
+// `lds`.  A failed HIP call is cleared from the runtime's error state.
+enum class Admit { fits, not_fits, attr_error, query_error };
+inline Admit admit_launch(const void* fn, int threads, size_t lds, bool set_attr, hipError_t* err = nullptr) {
+  hipError_t e = hipSuccess;
+  Admit a = Admit::fits;
+  int per_cu = 0;
+  if (set_attr && (e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
+    a = Admit::attr_error;
+  else if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds)) != hipSuccess)
+    a = Admit::query_error;
+  else if (per_cu < 1)
+    a = Admit::not_fits;
+  if (e != hipSuccess) (void)hipGetLastError();
+  if (err) *err = e;
+  return a;
+}
 
 // Measurement hooks: n launches, each bracketed by its own pair of HIP events on `st`,
 // *ms = sum of the per-launch elapsed times (so inter-launch gaps are not charged to

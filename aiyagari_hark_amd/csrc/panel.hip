@@ -230,13 +230,13 @@ static int sim_blocks(long long n) {
 }
 
 static int32_t ensure_panel_scratch(aiy_handle* h) {
-  if (h->partials_cap >= (size_t)kSimMaxBlocks) return AIY_OK;
-  AIY_HIP(h, hipMalloc((void**)&h->d_partials, sizeof(double) * kSimMaxBlocks));
+  if (h->cap_stream) return AIY_OK;   // (created last: the buffers are then in place and zeroed)
   const size_t tk = sizeof(unsigned) * (kTicketGroups + 1) * kTicketStride;
-  AIY_HIP(h, hipMalloc((void**)&h->d_ticket, tk));
-  AIY_HIP(h, hipMemset(h->d_ticket, 0, tk));
+  int32_t rc = h->partials.reserve(h, sizeof(double) * kSimMaxBlocks);
+  if (rc == AIY_OK) rc = h->ticket.reserve(h, tk);
+  if (rc) return rc;
+  AIY_HIP(h, hipMemset(h->ticket.get(), 0, tk));
   AIY_HIP(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
-  h->partials_cap = kSimMaxBlocks;
   return AIY_OK;
 }
 
@@ -291,7 +291,7 @@ extern "C" int32_t aiy_sim_periods(aiy_handle* h, const aiy_panel_model* model, 
   PanelRun r;
   r.n = n_local; r.offset = agent_offset; r.n_total = n_total; r.a = a; r.lab = lab; r.u = u; r.u_ld = u_ld;
   r.u_t0 = t0; r.emp = emp; r.emp_ld = emp_ld; r.seed = seed; r.ge_iter = ge_iter; r.sow = sow;
-  r.partials = h->d_partials; r.ticket = h->d_ticket;
+  r.partials = h->partials.as<double>(); r.ticket = h->ticket.as<unsigned>();
   r.hist_A = hist_A; r.hist_M = hist_M; r.finish = h->comm ? 0 : 1;
   const aiy_market mk = *mkt;
 
@@ -386,7 +386,7 @@ extern "C" int32_t aiy_sim_period_local(aiy_handle* h, const aiy_panel_model* mo
   if (rc) return rc;
   PanelRun r;
   r.n = n_local; r.offset = agent_offset; r.n_total = n_local; r.a = a; r.lab = lab; r.u = u; r.u_ld = n_local;
-  r.u_t0 = t; r.emp = emp; r.emp_ld = n_local; r.seed = seed; r.ge_iter = ge_iter; r.sow = sow; r.partials = h->d_partials; r.ticket = h->d_ticket;
+  r.u_t0 = t; r.emp = emp; r.emp_ld = n_local; r.seed = seed; r.ge_iter = ge_iter; r.sow = sow; r.partials = h->partials.as<double>(); r.ticket = h->ticket.as<unsigned>();
   r.hist_A = nullptr; r.hist_M = nullptr; r.finish = 0;
   hipLaunchKernelGGL(set_period_kernel, dim3(1), dim3(64), 0, st, sow, (int)t);
   if (h->use_resident && !emp && n_local >= kResMinAgents && resident_supported(P) && resident_aligned(a, lab) &&
@@ -451,7 +451,7 @@ extern "C" int32_t aiy_sim_kernel_time(aiy_handle* h, const aiy_panel_model* mod
   if (rc) return rc;
   PanelRun r;
   r.n = n_local; r.offset = 0; r.n_total = n_local; r.a = a; r.lab = lab; r.u = nullptr; r.u_ld = 0; r.u_t0 = 0;
-  r.emp = nullptr; r.emp_ld = 0; r.seed = seed; r.ge_iter = ge_iter; r.sow = sow; r.partials = h->d_partials; r.ticket = h->d_ticket;
+  r.emp = nullptr; r.emp_ld = 0; r.seed = seed; r.ge_iter = ge_iter; r.sow = sow; r.partials = h->partials.as<double>(); r.ticket = h->ticket.as<unsigned>();
   r.hist_A = nullptr; r.hist_M = nullptr; r.finish = 1;
   const int nb = sim_blocks(n_local);
   hipLaunchKernelGGL(set_period_kernel, dim3(1), dim3(64), 0, st, sow, 0);

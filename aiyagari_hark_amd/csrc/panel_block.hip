@@ -219,18 +219,15 @@ extern "C" int32_t aiy_sim_block_periods(aiy_handle* h, const aiy_panel_batch* m
   AIY_USE_STREAM(h, st);
   // per-calibration constants -> device scratch (stream-ordered copy of a pinned staging buffer)
   const size_t need = (size_t)M.n_cal * (sizeof(aiy_market) + sizeof(unsigned long long));
-  if (need > h->blk_cap) {
-    if (h->d_blk) (void)hipFree(h->d_blk);
-    if (h->h_blk) (void)hipHostFree(h->h_blk);
-    h->d_blk = nullptr; h->h_blk = nullptr; h->blk_cap = 0;
-    AIY_HIP(h, hipMalloc(&h->d_blk, need));
-    AIY_HIP(h, hipHostMalloc(&h->h_blk, need, hipHostMallocDefault));
-    h->blk_cap = need;
-  }
+  int32_t rc = h->blk_dev.reserve(h, need);
+  if (rc == AIY_OK) rc = h->blk_pin.reserve(h, need);
+  if (rc) return rc;
+  char* d_blk = h->blk_dev.as<char>();
+  char* h_blk = h->blk_pin.as<char>();
   AIY_HIP(h, hipStreamSynchronize(st));   // the staging buffer may still feed a previous copy
-  std::memcpy(h->h_blk, markets, sizeof(aiy_market) * M.n_cal);
-  std::memcpy((char*)h->h_blk + sizeof(aiy_market) * M.n_cal, seeds, sizeof(unsigned long long) * M.n_cal);
-  AIY_HIP(h, hipMemcpyAsync(h->d_blk, h->h_blk, need, hipMemcpyHostToDevice, st));
+  std::memcpy(h_blk, markets, sizeof(aiy_market) * M.n_cal);
+  std::memcpy(h_blk + sizeof(aiy_market) * M.n_cal, seeds, sizeof(unsigned long long) * M.n_cal);
+  AIY_HIP(h, hipMemcpyAsync(d_blk, h_blk, need, hipMemcpyHostToDevice, st));
   BatchDev B;
   B.n_cal = M.n_cal; B.S = M.S; B.n_M = M.n_M; B.n_a = M.n_a; B.n_lab = M.n_lab; B.act_T = act_T;
   B.unemployed = M.unemployed != 0;
@@ -239,8 +236,8 @@ extern "C" int32_t aiy_sim_block_periods(aiy_handle* h, const aiy_panel_batch* m
   B.lab_level = M.lab_level; B.lab_cdf = M.lab_cdf; B.mrkv_hist = M.mrkv_hist;
   BlockRun r;
   r.n = n_agents; r.a = a; r.lab = lab; r.u = u; r.emp = emp;
-  r.mk = reinterpret_cast<const aiy_market*>(h->d_blk);
-  r.seeds = reinterpret_cast<const unsigned long long*>((char*)h->d_blk + sizeof(aiy_market) * M.n_cal);
+  r.mk = reinterpret_cast<const aiy_market*>(d_blk);
+  r.seeds = reinterpret_cast<const unsigned long long*>(d_blk + sizeof(aiy_market) * M.n_cal);
   r.ge_iter = ge_iter; r.t0 = t0; r.n_periods = n_periods; r.sow = sow; r.hist_A = hist_A; r.hist_M = hist_M;
   // 2 agents per lane up to 2048 agents (more waves to hide the lookup latency), then 4
   const int A = n_agents <= 2048 ? 2 : 4;

@@ -484,15 +484,6 @@ bool resident_supported(const PanelDev& P) {
   return res_hdr_bytes(P.tab.g.n_cells) <= kResHdrMaxBytes && P.n_M <= kResMaxM;
 }
 
-static int32_t ensure_res_scratch(aiy_handle* h) {
-  if (!h->d_res_sync) {
-    AIY_HIP(h, hipMalloc((void**)&h->d_res_sync, kResSyncBytes));
-  }
-  for (hipEvent_t& e : h->res_ev)
-    if (!e) AIY_HIP(h, hipEventCreate(&e));
-  return AIY_OK;
-}
-
 // Launch the resident kernel for periods [t0, t0 + n_periods) (single rank).
 int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, long long n, double* a, uint8_t* lab,
                         const double* u, long long u_ld, unsigned long long seed, unsigned ge_iter, int t0,
@@ -518,8 +509,9 @@ int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, 
       G = Gs;
     }
   }
-  int32_t rc = ensure_res_scratch(h);
+  const int32_t rc = h->res_sync.reserve(h, kResSyncBytes);
   if (rc) return rc;
+  AIY_HIP(h, h->res_timer.ensure());
   // [shape][in LDS][sharded]
   const void* kernels[3][2][2] = {
       {{reinterpret_cast<const void*>(sim_resident_kernel<512, 8, false, true, false>),
@@ -545,18 +537,18 @@ int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, 
   ResRun r;
   r.n = n; r.offset = offset; r.chunk = G.chunk; r.a = a; r.lab = lab; r.u = u; r.u_ld = u_ld; r.seed = seed;
   r.ge_iter = ge_iter; r.t0 = t0; r.n_periods = n_periods; r.sow = sow;
-  r.gran = reinterpret_cast<unsigned long long*>(h->d_res_sync);
-  r.tmo = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(h->d_res_sync) + kResGranBytes);
+  r.gran = h->res_sync.as<unsigned long long>();
+  r.tmo = reinterpret_cast<unsigned*>(h->res_sync.as<char>() + kResGranBytes);
   r.hist_A = hist_A; r.hist_M = hist_M;
   r.flags = flags;
   r.n_total = n_total > 0 ? n_total : n;
   // granule tags unique over the handle's launches: the slots need zeroing only when the tag
   // counter starts over (the first launch, or after 2^31 periods)
   if (h->res_epoch == 0 || h->res_epoch > 0x7fffffffu) {
-    AIY_HIP(h, hipMemsetAsync(h->d_res_sync, 0, kResSyncBytes, st));
+    AIY_HIP(h, hipMemsetAsync(h->res_sync.get(), 0, kResSyncBytes, st));
     h->res_epoch = 0;
   } else if (!(flags & kResKeepTmo)) {
-    AIY_HIP(h, hipMemsetAsync(reinterpret_cast<char*>(h->d_res_sync) + kResGranBytes, 0, sizeof(unsigned), st));
+    AIY_HIP(h, hipMemsetAsync(r.tmo, 0, sizeof(unsigned), st));
   }
   r.ep0 = h->res_epoch;
   h->res_epoch += (unsigned)n_periods + 1u;
@@ -574,34 +566,32 @@ int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, 
   // cooperative one without its per-launch host cost (MI355X_MICROARCH.md, coop-launch),
   // and the in-kernel sweep is bounded by a wall-clock timeout either way.
   if (fn != h->res_occ_fn || G.lds != h->res_occ_lds) {   // the occupancy query once per shape
-    int per_cu = 0;
-    AIY_HIP(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, sh.th, G.lds));
-    if (per_cu < 1) return fail(h, AIY_ERR_UNSUPPORTED, "resident panel: workgroup does not fit a CU");
+    hipError_t e = hipSuccess;   // (the dynamic-LDS limit of every form is raised above, once)
+    const Admit adm = admit_launch(fn, sh.th, G.lds, false, &e);
+    if (adm == Admit::query_error)
+      return fail(h, AIY_ERR_HIP, "hipOccupancyMaxActiveBlocksPerMultiprocessor failed: %s", hipGetErrorString(e));
+    if (adm != Admit::fits) return fail(h, AIY_ERR_UNSUPPORTED, "resident panel: workgroup does not fit a CU");
     h->res_occ_fn = fn;
     h->res_occ_lds = G.lds;
   }
   // HIP events bracket the single-rank launches (aiy_panel_launch_stats); the sharded per-period
   // launches are timed by the caller's clock
   const bool timed = !(flags & kResSharded);
-  if (timed) AIY_HIP(h, hipEventRecord(h->res_ev[0], st));
+  if (timed) AIY_HIP(h, h->res_timer.begin(st));
   AIY_HIP(h, hipLaunchKernel(fn, dim3(G.nb), dim3(sh.th), args, G.lds, st));
-  if (timed) AIY_HIP(h, hipEventRecord(h->res_ev[1], st));
+  if (timed) AIY_HIP(h, h->res_timer.end(st));
   h->res_periods += n_periods;
   return AIY_OK;
 }
 
 // Timeout word of the last resident launch (0 = fine).  Synchronises `st`.
 int32_t resident_status(aiy_handle* h, hipStream_t st, bool timed) {
-  if (!h->d_res_sync) return AIY_OK;
+  if (!h->res_sync.get()) return AIY_OK;
   unsigned tmo = 0;
-  AIY_HIP(h, hipMemcpyAsync(&tmo, reinterpret_cast<char*>(h->d_res_sync) + kResGranBytes, sizeof(unsigned),
+  AIY_HIP(h, hipMemcpyAsync(&tmo, h->res_sync.as<char>() + kResGranBytes, sizeof(unsigned),
                             hipMemcpyDeviceToHost, st));
   AIY_HIP(h, hipStreamSynchronize(st));
-  float ms = 0.f;
-  if (timed && hipEventElapsedTime(&ms, h->res_ev[0], h->res_ev[1]) == hipSuccess) {
-    h->res_ms_sum += ms;
-    h->res_launches += 1;
-  }
+  if (timed) h->res_timer.collect();
   if (tmo) return fail(h, AIY_ERR_STATE, "resident panel: partial-sum exchange timed out (workgroups not co-resident?)");
   return AIY_OK;
 }
@@ -613,13 +603,8 @@ int32_t resident_status(aiy_handle* h, hipStream_t st, bool timed) {
 extern "C" int32_t aiy_panel_launch_stats(aiy_handle* h, double* ms_sum, int64_t* launches, int64_t* periods,
                                           int32_t reset) {
   if (!h) return AIY_ERR_ARG;
-  if (ms_sum) *ms_sum = h->res_ms_sum;
-  if (launches) *launches = h->res_launches;
+  h->res_timer.read(ms_sum, launches, reset != 0);
   if (periods) *periods = h->res_periods;
-  if (reset) {
-    h->res_ms_sum = 0.0;
-    h->res_launches = 0;
-    h->res_periods = 0;
-  }
+  if (reset) h->res_periods = 0;
   return AIY_OK;
 }

@@ -95,16 +95,6 @@ __global__ void stats_interp_kernel(const double* __restrict__ sorted, const dou
   }
 }
 
-static int32_t grow(aiy_handle* h, void** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return AIY_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  AIY_HIP(h, hipMalloc(p, bytes));
-  *cap = bytes;
-  return AIY_OK;
-}
-
 }  // namespace aiy
 
 using namespace aiy;
@@ -137,9 +127,9 @@ extern "C" int32_t aiy_wealth_stats(aiy_handle* h, const double* data, const dou
                                      rocprim::plus<double>(), st));
   const size_t head = (nbuf * nb + small + 255) / 256 * 256;   // rocPRIM temp 256-aligned
   const size_t tmp = (tmp_sort > tmp_scan ? tmp_sort : tmp_scan) + 256;
-  rc = grow(h, &h->d_stats, &h->stats_cap, head + tmp);
+  rc = h->stats.reserve(h, head + tmp);
   if (rc) return rc;
-  char* base = reinterpret_cast<char*>(h->d_stats);
+  char* base = h->stats.as<char>();
   double* sorted = reinterpret_cast<double*>(base);
   double* cd = reinterpret_cast<double*>(base + nb);
   double* ws = weights ? reinterpret_cast<double*>(base + 2 * nb) : nullptr;

@@ -465,9 +465,10 @@ void tr_launch_marginal(long long n_dist, int S, int n_a, const double* mass, do
 // ---------------------------------------------------------------------------------
 // Work space (caller-owned): every region starts on a 256-byte boundary.
 // ---------------------------------------------------------------------------------
-struct TrLayout {
-  size_t tab, jb, alt, kpart, cpart, ks, c, flag, total;   // byte offsets
-  size_t tab_doubles;                                      // one [n_cal][S][n_a + 1] table
+struct TrWork {
+  double *tab, *alt, *kpart, *cpart, *ks, *c;   // tab: (m, c) x ping-pong; alt: ping-pong partner of mass
+  int *jb, *flag;
+  size_t bytes, tab_doubles;                    // tab_doubles: one [n_cal][S][n_a + 1] table
   int nblk;
 };
 
@@ -475,20 +476,19 @@ static bool tr_sizes_ok(int n_cal, int S, int n_a, int T) {
   return tr_pull_sizes_ok(n_cal, S, n_a) && T >= 1;
 }
 
-static TrLayout tr_layout(int n_cal, int S, int n_a, int T) {
-  TrLayout L;
+static TrWork tr_work(Carve c, int n_cal, int S, int n_a, int T) {
+  TrWork L;
   L.nblk = tr_nblk(n_a);
   L.tab_doubles = (size_t)n_cal * S * (n_a + 1);
-  size_t o = 0;
-  L.tab = o;   o += tab_align(4 * L.tab_doubles * sizeof(double));                      // (m, c) x ping-pong
-  L.jb = o;    o += tab_align((size_t)T * n_cal * S * (n_a + 1) * sizeof(int));
-  L.alt = o;   o += tab_align((size_t)n_cal * S * n_a * sizeof(double));               // ping-pong partner of mass
-  L.kpart = o; o += tab_align((size_t)(T + 1) * n_cal * L.nblk * sizeof(double));
-  L.cpart = o; o += tab_align((size_t)T * n_cal * L.nblk * sizeof(double));
-  L.ks = o;    o += tab_align((size_t)n_cal * (T + 1) * sizeof(double));
-  L.c = o;     o += tab_align((size_t)n_cal * T * sizeof(double));
-  L.flag = o;  o += 256;
-  L.total = o;
+  L.tab = c.take<double>(4 * L.tab_doubles);
+  L.jb = c.take<int>((size_t)T * n_cal * S * (n_a + 1));
+  L.alt = c.take<double>((size_t)n_cal * S * n_a);
+  L.kpart = c.take<double>((size_t)(T + 1) * n_cal * L.nblk);
+  L.cpart = c.take<double>((size_t)T * n_cal * L.nblk);
+  L.ks = c.take<double>((size_t)n_cal * (T + 1));
+  L.c = c.take<double>((size_t)n_cal * T);
+  L.flag = c.take<int>(256 / sizeof(int));
+  L.bytes = c.bytes();
   return L;
 }
 
@@ -498,7 +498,7 @@ using namespace aiy;
 
 extern "C" int64_t aiy_transition_work_bytes(int32_t n_cal, int32_t S, int32_t n_a, int32_t T) {
   if (!tr_sizes_ok(n_cal, S, n_a, T)) return -1;
-  return (int64_t)tr_layout(n_cal, S, n_a, T).total;
+  return (int64_t)tr_work(Carve(), n_cal, S, n_a, T).bytes;
 }
 
 extern "C" int32_t aiy_transition_backward(aiy_handle* h, const aiy_transition_model* M, void* work, int32_t* lo,
@@ -515,8 +515,8 @@ extern "C" int32_t aiy_transition_backward(aiy_handle* h, const aiy_transition_m
   AIY_HIP(h, hipSetDevice(h->device));
   hipStream_t st = as_stream(stream);
   AIY_USE_STREAM(h, st);
-  const TrLayout L = tr_layout(n_cal, S, n_a, T);
-  double* tab = reinterpret_cast<double*>(static_cast<char*>(work) + L.tab);
+  const TrWork L = tr_work(Carve(work), n_cal, S, n_a, T);
+  double* tab = L.tab;
   auto m_buf = [&](int b) { return tab + (size_t)(2 * b) * L.tab_doubles; };
   auto c_buf = [&](int b) { return tab + (size_t)(2 * b + 1) * L.tab_doubles; };
   const size_t per = (size_t)n_cal * S * n_a;   // one period's lottery
@@ -561,21 +561,18 @@ static int32_t tr_forward_sweep(aiy_handle* h, int32_t n_cal, int32_t S, int32_t
   AIY_HIP(h, hipSetDevice(h->device));
   hipStream_t st = as_stream(stream);
   AIY_USE_STREAM(h, st);
-  const TrLayout L = tr_layout(n_cal, S, n_a, T);
-  char* wb = static_cast<char*>(work);
-  int* jb = reinterpret_cast<int*>(wb + L.jb);
-  double* alt = reinterpret_cast<double*>(wb + L.alt);
-  double* d_Ks = reinterpret_cast<double*>(wb + L.ks);
-  double* d_C = reinterpret_cast<double*>(wb + L.c);
-  int* d_flag = reinterpret_cast<int*>(wb + L.flag);
+  const TrWork L = tr_work(Carve(work), n_cal, S, n_a, T);
+  int* jb = L.jb;
+  double *alt = L.alt, *d_Ks = L.ks, *d_C = L.c;
+  int* d_flag = L.flag;
   // inverse index of every period and the row check, before anything is pushed
   rc = tr_build_ranges(h, n_cal, S, n_a, T, lo, jb, d_flag, st);
   if (rc) return rc;
   TrFwd A;
   A.n_cal = n_cal; A.S = S; A.n_a = n_a; A.T = T; A.nblk = L.nblk;
   A.wlo = wlo; A.jb = jb; A.P = P; A.a_grid = a_grid; A.R = R; A.w = w; A.lab = lab;
-  A.Kpart = reinterpret_cast<double*>(wb + L.kpart);
-  A.Cpart = reinterpret_cast<double*>(wb + L.cpart);
+  A.Kpart = L.kpart;
+  A.Cpart = L.cpart;
   const bool with_c = C_out != nullptr;
   const size_t per_marg = (size_t)n_cal * n_a;
   hipLaunchKernelGGL(tr_K0_kernel, dim3(L.nblk, n_cal), dim3(kTrBlock), 0, st, A, (const double*)mass);

@@ -216,9 +216,10 @@ __global__ __launch_bounds__(256) void jac_sum_kernel(int n_cal, int nchunk, siz
 // ---------------------------------------------------------------------------------
 // Work space (caller-owned): every region starts on a 256-byte boundary.
 // ---------------------------------------------------------------------------------
-struct JacLayout {
-  size_t jb, g, part, flag, total;   // byte offsets
-  size_t per;                        // one period: n_cal S n_a
+struct JacWork {
+  int *jb, *flag;       // jb: fan-out, T + 1 periods
+  double *g, *part;     // g: G ping-pong
+  size_t bytes, per;    // per: one period, n_cal S n_a
   int nchunk, nblk;
 };
 
@@ -229,17 +230,16 @@ static bool jac_sizes_ok(int n_cal, int S, int n_a, int T) {
   return nchunk <= 65535 && tiles <= 2147483647LL;
 }
 
-static JacLayout jac_layout(int n_cal, int S, int n_a, int T) {
-  JacLayout L;
+static JacWork jac_work(Carve c, int n_cal, int S, int n_a, int T) {
+  JacWork L;
   L.per = (size_t)n_cal * S * n_a;
   L.nchunk = (int)(((size_t)S * n_a + kJacChunk - 1) / kJacChunk);
   L.nblk = tr_nblk(n_a);
-  size_t o = 0;
-  L.jb = o;   o += tab_align((size_t)(T + 1) * n_cal * S * (n_a + 1) * sizeof(int));               // fan-out: T + 1 periods
-  L.g = o;    o += tab_align(2 * L.per * sizeof(double));                                           // G ping-pong
-  L.part = o; o += tab_align((size_t)n_cal * L.nchunk * T * 2 * (T + 1) * sizeof(double));
-  L.flag = o; o += 256;
-  L.total = o;
+  L.jb = c.take<int>((size_t)(T + 1) * n_cal * S * (n_a + 1));
+  L.g = c.take<double>(2 * L.per);
+  L.part = c.take<double>((size_t)n_cal * L.nchunk * T * 2 * (T + 1));
+  L.flag = c.take<int>(256 / sizeof(int));
+  L.bytes = c.bytes();
   return L;
 }
 
@@ -254,7 +254,7 @@ using namespace aiy;
 
 extern "C" int64_t aiy_jacobian_work_bytes(int32_t n_cal, int32_t S, int32_t n_a, int32_t T) {
   if (!jac_sizes_ok(n_cal, S, n_a, T)) return -1;
-  return (int64_t)jac_layout(n_cal, S, n_a, T).total;
+  return (int64_t)jac_work(Carve(), n_cal, S, n_a, T).bytes;
 }
 
 extern "C" int32_t aiy_jacobian_fanout(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T, int32_t n_t,
@@ -268,11 +268,10 @@ extern "C" int32_t aiy_jacobian_fanout(aiy_handle* h, int32_t n_cal, int32_t S, 
   AIY_HIP(h, hipSetDevice(h->device));
   hipStream_t st = as_stream(stream);
   AIY_USE_STREAM(h, st);
-  const JacLayout L = jac_layout(n_cal, S, n_a, T);
-  char* wb = static_cast<char*>(work);
-  int* jb = reinterpret_cast<int*>(wb + L.jb);
+  const JacWork L = jac_work(Carve(work), n_cal, S, n_a, T);
+  int* jb = L.jb;
   // inverse index of every period and the row check, before anything is written
-  rc = tr_build_ranges(h, n_cal, S, n_a, n_t, lo, jb, reinterpret_cast<int*>(wb + L.flag), st);
+  rc = tr_build_ranges(h, n_cal, S, n_a, n_t, lo, jb, L.flag, st);
   if (rc) return rc;
   JacFan A;
   A.n_cal = n_cal; A.S = S; A.n_a = n_a; A.wlo = wlo; A.jb = jb; A.P = P;
@@ -306,13 +305,11 @@ extern "C" int32_t aiy_jacobian_expectation(aiy_handle* h, int32_t n_cal, int32_
   AIY_HIP(h, hipSetDevice(h->device));
   hipStream_t st = as_stream(stream);
   AIY_USE_STREAM(h, st);
-  const JacLayout L = jac_layout(n_cal, S, n_a, T);
-  char* wb = static_cast<char*>(work);
+  const JacWork L = jac_work(Carve(work), n_cal, S, n_a, T);
   // the gather reads G at lo and lo + 1: the lottery passes the forward sweep's row check first
-  rc = tr_build_ranges(h, n_cal, S, n_a, 1, lo, reinterpret_cast<int*>(wb + L.jb), reinterpret_cast<int*>(wb + L.flag),
-                       st);
+  rc = tr_build_ranges(h, n_cal, S, n_a, 1, lo, L.jb, L.flag, st);
   if (rc) return rc;
-  double* G = reinterpret_cast<double*>(wb + L.g);
+  double* G = L.g;
   JacExp A;
   A.S = S; A.n_a = n_a; A.lo = lo; A.wlo = wlo; A.P = P; A.a_grid = a_grid;
   const dim3 grid(L.nblk, n_cal);
@@ -335,13 +332,13 @@ extern "C" int32_t aiy_jacobian_contract(aiy_handle* h, int32_t n_cal, int32_t S
   AIY_HIP(h, hipSetDevice(h->device));
   hipStream_t st = as_stream(stream);
   AIY_USE_STREAM(h, st);
-  const JacLayout L = jac_layout(n_cal, S, n_a, T);
+  const JacWork L = jac_work(Carve(work), n_cal, S, n_a, T);
   JacCon A;
   A.n_cal = n_cal; A.T = T; A.n_col = T + 1; A.nchunk = L.nchunk;
   A.nct = (2 * A.n_col + kJacTile - 1) / kJacTile;
   A.N = (size_t)S * n_a;
   A.E = E; A.D0 = dD_R; A.D1 = dD_w;
-  A.part = reinterpret_cast<double*>(static_cast<char*>(work) + L.part);
+  A.part = L.part;
   const unsigned tiles = (unsigned)((T + kJacTile - 1) / kJacTile) * (unsigned)A.nct;
   hipLaunchKernelGGL(jac_contract_kernel, dim3(tiles, L.nchunk, n_cal), dim3(kJacBlock), 0, st, A);
   const size_t per = (size_t)T * 2 * A.n_col;

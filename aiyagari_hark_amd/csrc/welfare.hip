@@ -212,20 +212,20 @@ __global__ __launch_bounds__(256) void value_ce_kernel(size_t n, size_t per, con
 }
 
 // Work space (caller-owned): the two mixed values, then the convergence slots.
-struct ValLayout {
-  size_t g, slots, total;   // byte offsets
-  size_t per;               // n_cal S n_a
+struct ValWork {
+  double* g;
+  unsigned long long* slots;
+  size_t bytes, per;   // per: n_cal S n_a
   int nblk;
 };
 
-static ValLayout val_layout(int n_cal, int S, int n_a) {
-  ValLayout L;
+static ValWork val_work(Carve c, int n_cal, int S, int n_a) {
+  ValWork L;
   L.per = (size_t)n_cal * S * n_a;
   L.nblk = tr_nblk(n_a);
-  size_t o = 0;
-  L.g = o;     o += tab_align(2 * L.per * sizeof(double));
-  L.slots = o; o += tab_align((size_t)n_cal * kValSlots * sizeof(unsigned long long));
-  L.total = o;
+  L.g = c.take<double>(2 * L.per);
+  L.slots = c.take<unsigned long long>((size_t)n_cal * kValSlots);
+  L.bytes = c.bytes();
   return L;
 }
 
@@ -241,7 +241,7 @@ using namespace aiy;
 
 extern "C" int64_t aiy_value_work_bytes(int32_t n_cal, int32_t S, int32_t n_a) {
   if (!tr_pull_sizes_ok(n_cal, S, n_a)) return -1;
-  return (int64_t)val_layout(n_cal, S, n_a).total;
+  return (int64_t)val_work(Carve(), n_cal, S, n_a).bytes;
 }
 
 extern "C" int32_t aiy_value_backward(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
@@ -257,8 +257,8 @@ extern "C" int32_t aiy_value_backward(aiy_handle* h, int32_t n_cal, int32_t S, i
   if (!V_term || !work || !V0_out) return fail(h, AIY_ERR_ARG, "null buffer");
   AIY_HIP(h, hipSetDevice(h->device));
   hipStream_t st = as_stream(stream);
-  const ValLayout L = val_layout(n_cal, S, n_a);
-  double* G = reinterpret_cast<double*>(static_cast<char*>(work) + L.g);
+  const ValWork L = val_work(Carve(work), n_cal, S, n_a);
+  double* G = L.g;
   ValArgs A;
   A.S = S; A.n_a = n_a; A.pstride = T + 1;
   A.lo = lo; A.wlo = wlo; A.P = P; A.a_grid = a_grid; A.R = R; A.w = w; A.lab = lab; A.beta = beta; A.crra = crra;
@@ -293,10 +293,9 @@ extern "C" int32_t aiy_value_stationary(aiy_handle* h, int32_t n_cal, int32_t S,
   if (chunk <= 0) chunk = 32;
   AIY_HIP(h, hipSetDevice(h->device));
   hipStream_t st = as_stream(stream);
-  const ValLayout L = val_layout(n_cal, S, n_a);
-  char* wb = static_cast<char*>(work);
-  double* G = reinterpret_cast<double*>(wb + L.g);
-  unsigned long long* slots = reinterpret_cast<unsigned long long*>(wb + L.slots);
+  const ValWork L = val_work(Carve(work), n_cal, S, n_a);
+  double* G = L.g;
+  unsigned long long* slots = L.slots;
   const size_t n_slots = (size_t)n_cal * kValSlots;
   AIY_HIP(h, hipMemsetAsync(slots, 0, n_slots * sizeof(unsigned long long), st));
   ValArgs A;
@@ -339,16 +338,12 @@ extern "C" int32_t aiy_value_reduce(aiy_handle* h, int32_t n_cal, int32_t S, int
   hipStream_t st = as_stream(stream);
   AIY_USE_STREAM(h, st);
   const size_t n_rows = (size_t)n_cal * S;
-  if (n_rows > h->welf_cap) {
-    if (h->d_welf) (void)hipFree(h->d_welf);
-    h->d_welf = nullptr;
-    h->welf_cap = 0;
-    AIY_HIP(h, hipMalloc((void**)&h->d_welf, n_rows * sizeof(double)));
-    h->welf_cap = n_rows;
-  }
-  hipLaunchKernelGGL(value_reduce_kernel, dim3((unsigned)n_rows), dim3(kTrBlock), 0, st, n_a, mass, V, h->d_welf);
+  rc = h->welf.reserve(h, n_rows * sizeof(double));
+  if (rc) return rc;
+  double* d_welf = h->welf.as<double>();
+  hipLaunchKernelGGL(value_reduce_kernel, dim3((unsigned)n_rows), dim3(kTrBlock), 0, st, n_a, mass, V, d_welf);
   AIY_CHECK_LAUNCH(h);
-  AIY_HIP(h, hipMemcpyAsync(W_out, h->d_welf, n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
+  AIY_HIP(h, hipMemcpyAsync(W_out, d_welf, n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
   AIY_HIP(h, hipStreamSynchronize(st));
   return AIY_OK;
 }
