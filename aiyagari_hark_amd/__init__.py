@@ -11,7 +11,9 @@ bisection on r, Young-lottery histogram, Rouwenhorst) in
 :mod:`aiyagari_hark_amd.stationary`; perfect-foresight transition paths after a shock
 (``steady_state``, ``household_block``, ``solve_transition``) and the sequence-space Jacobian
 of the household block (``household_jacobian``, ``impulse_response``) in
-:mod:`aiyagari_hark_amd.transition`; wealth statistics of the panel and of histogram
+:mod:`aiyagari_hark_amd.transition`; the economy with aggregate TFP risk to first order
+(``policy_jacobian``, ``linear_model``, ``simulate``, ``saving_rule``) in
+:mod:`aiyagari_hark_amd.aggregate`; wealth statistics of the panel and of histogram
 distributions and paths (``histogram_stats``, ``batch_wealth_stats``, ``path_wealth_stats``) in
 :mod:`aiyagari_hark_amd.stats`; values on the histogram and consumption-equivalent welfare gains
 (``stationary_value``, ``path_value``, ``welfare.welfare``) in :mod:`aiyagari_hark_amd.welfare`.
@@ -31,6 +33,10 @@ def __getattr__(name):
                 "HouseholdJacobian", "impulse_response", "path_wealth_stats"):
         from . import transition
         return getattr(transition, name)
+    if name in ("policy_jacobian", "PolicyJacobian", "ar1", "linear_model", "AggregateModel", "moments", "expectations",
+                "simulate", "AggregateSimulation", "saving_rule"):
+        from . import aggregate
+        return getattr(aggregate, name)
     if name in ("histogram_stats", "batch_wealth_stats", "WealthStats"):
         from . import stats
         return getattr(stats, name)

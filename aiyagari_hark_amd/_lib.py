@@ -177,6 +177,10 @@ SIGNATURES = {
                                                   vp, vp, vp, vp, vp, vp, vp]),
     "aiy_jacobian_contract": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                vp, vp, vp, vp, vp, vp]),
+    "aiy_lottery_mean": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp,
+                                          vp, vp]),
+    "aiy_aggregate_lotteries": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "aiy_wealth_stats": (ctypes.c_int32, [vp, vp, vp, ctypes.c_int64, c_double_p, ctypes.c_int32, c_double_p,
                                           c_double_p, vp]),
     "aiy_dist_stats_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),

@@ -455,6 +455,21 @@ def jacobian_contract(device, E, dD_R, dD_w, work, F=None, stream=None):
     return F
 
 
+def _shocked_backward(batch, Rs, w, T, h, shock, m_term, c_term, sweep):
+    """One backward sweep of the Jacobians over T + 2 periods on the constant prices (Rs, w)
+    [n_cal], with R[T] (shock "R") or w[T] (shock "w") moved by h, or neither (the ghost):
+    fills the T + 1 lotteries of ``sweep`` (TransitionBuffers of T + 1 periods)."""
+    R = np.repeat(Rs[:, None], T + 2, axis=1)
+    W = np.repeat(np.asarray(w)[:, None], T + 2, axis=1)
+    if shock == "R":
+        R[:, T] += h
+    elif shock == "w":
+        W[:, T] += h
+    dev = batch.device
+    transition_backward(batch, torch.as_tensor(R).to(dev), torch.as_tensor(W).to(dev), m_term, c_term, sweep,
+                        export_policy=False)
+
+
 def household_jacobian(batch, r, T, h=1e-5, m_term=None, c_term=None, buffers=None, timings=None):
     """Sequence-space Jacobian of the household block of every calibration of ``batch`` at its
     steady state (interest rate ``r`` [n_cal], tables ``batch.last_tables``, mass ``batch.mass``)
@@ -493,14 +508,7 @@ def household_jacobian(batch, r, T, h=1e-5, m_term=None, c_term=None, buffers=No
             t_last[0] = now
 
     def step_of_sweep(shock, out):
-        R = np.repeat(Rs[:, None], T + 2, axis=1)
-        W = np.repeat(np.asarray(w)[:, None], T + 2, axis=1)
-        if shock == "R":
-            R[:, T] += h
-        elif shock == "w":
-            W[:, T] += h
-        transition_backward(batch, torch.as_tensor(R).to(dev), torch.as_tensor(W).to(dev), m_term, c_term,
-                            buffers.sweep, export_policy=False)
+        _shocked_backward(batch, Rs, w, T, h, shock, m_term, c_term, buffers.sweep)
         stage("backward")
         jacobian_fanout(batch, buffers.sweep.lo, buffers.sweep.wlo, mass, out, buffers.work, T)
         stage("fanout")

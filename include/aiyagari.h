@@ -632,6 +632,28 @@ int32_t aiy_jacobian_contract(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n
                               const double* dD_R, const double* dD_w, void* work, double* F_out,
                               aiy_stream stream);
 
+/* ------- aggregate risk with linearised policies (build-defined) ------- */
+
+/* The savings policy a lottery stands for, out = wlo a[lo] + (1 - wlo) a[lo + 1] element by
+ * element (a = the calibration's row of a_grid [n_cal][n_a]), for the n_t periods of a lottery.
+ *   lo / wlo / out: [n_t][n_cal][S][n_a]
+ * lo is read as held to [0, n_a - 2].  Asynchronous. */
+int32_t aiy_lottery_mean(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t n_t, const int32_t* lo,
+                         const double* wlo, const double* a_grid, double* out, aiy_stream stream);
+
+/* Young lotteries of n_p periods from linearised policies, on the f64 matrix instruction:
+ *   a'[p][cal][s][j] = a_star[cal][s][j] + sum_k op[k][cal][s][j] X[cal][p][k],  k < 2 (T + 1),
+ * op[k] = dA_R[k] for k <= T and dA_w[k - T - 1] after it; k ascends, the sum is added to
+ * a_star last, a' is clamped to [a_0, a_{n_a - 1}] of the calibration's grid, and
+ *   lo = clip(upper_bound(a, a') - 1, 0, n_a - 2),  wlo = clip((a[lo+1] - a') / (a[lo+1] - a[lo]), 0, 1).
+ * A period's lottery has the same bits whatever n_p, its place among the periods and the batch.
+ *   a_star: [n_cal][S][n_a]; dA_R / dA_w: [T+1][n_cal][S][n_a]; X: [n_cal][n_p][2(T+1)];
+ *   lo_out / wlo_out: [n_p][n_cal][S][n_a], the lottery aiy_transition_forward takes
+ * AIY_ERR_ARG, nothing written, for T < 1, n_p < 1, bad sizes or a null buffer.  Asynchronous. */
+int32_t aiy_aggregate_lotteries(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T, int32_t n_p,
+                                const double* a_star, const double* dA_R, const double* dA_w, const double* X,
+                                const double* a_grid, int32_t* lo_out, double* wlo_out, aiy_stream stream);
+
 /* ------------------- wealth-distribution statistics ------------------- */
 
 /* HARK 0.12 get_lorenz_shares(data, weights, percentiles) and get_percentiles(...) of a
