@@ -193,6 +193,12 @@ __device__ __forceinline__ void egm_phase1(const EgmDev& A, const double* __rest
     const double* __restrict__ ccal = c_next + (size_t)cal * S * n_M * n1;
     const int n_sp = (S - wave + kEgmWaves - 1) / kEgmWaves;
     const int nrr = n_sp * ROWS;
+    // S < 4: a wave that owns no next state issues no window load and reads no hint (the
+    // clamp in fetch would name row -1); it goes on to the block's barrier and phase 2.
+    // wave-uniform; no such wave exists at the compile-time state counts
+    if constexpr (SC < kEgmWaves) {
+      if (nrr == 0) return;
+    }
     auto row_of = [&](int rr, int& sp, int& r) {
       sp = wave + kEgmWaves * (ROWS == 2 ? rr >> 1 : rr);
       r = ROWS == 2 ? rr & 1 : 0;
