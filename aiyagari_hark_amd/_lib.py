@@ -44,6 +44,7 @@ AIY_OPT_HIST_PULL = 15
 AIY_OPT_GE_LOOSE_HIST = 17
 AIY_OPT_RESIDENT_SHAPE_STREAM = 18
 AIY_OPT_GE_ANDERSON = 23
+AIY_OPT_HIST_IID = 24
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -157,6 +158,7 @@ SIGNATURES = {
     "aiy_ge_last_profile": (ctypes.c_int32, [vp, c_double_p, ctypes.c_int32]),
     "aiy_ge_last_eval_log": (ctypes.c_int32, [vp, c_double_p, ctypes.c_int32]),
     "aiy_ge_last_rounds": (ctypes.c_int32, [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "aiy_ge_last_iid_cells": (ctypes.c_int32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     "aiy_ge_launch_stats": (ctypes.c_int32, [vp, c_double_p, ctypes.POINTER(ctypes.c_int64), c_double_p, c_double_p,
                                              ctypes.c_int32]),
     "aiy_ge_stationary_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),

@@ -88,6 +88,13 @@ constexpr bool kGeFuseA = true;
 #define AIY_FUSEA_KC2 0
 #endif
 constexpr bool kGeFuseAKc2 = AIY_FUSEA_KC2 != 0;
+// The asset-grid solve of an i.i.d. cell (hist_bicg.h IID) at two columns per thread: its vectors are
+// one value per column, all in registers, so the register pressure that ruled the riding reduction
+// out above is gone; the last wave still owns columns.  -DAIY_IID_FUSEA_KC2=0|1 builds either.
+#ifndef AIY_IID_FUSEA_KC2
+#define AIY_IID_FUSEA_KC2 0
+#endif
+constexpr bool kGeIidFuseAKc2 = AIY_IID_FUSEA_KC2 != 0;
 template <int NW>
 constexpr size_t ge_egm_lds() { return (size_t)NW * (8 * kTile + 4 * kWin) * sizeof(double); }   // V tiles + windows
 
@@ -109,6 +116,8 @@ struct GeRun {
   int max_steps, max_cyc, max_hist;
   int warm_hist, warm_egm, secant, loose, extrap;
   int extrap_period;      // EGM cycles between extrapolation checks (>= 4)
+  int iid_on;             // AIY_OPT_HIST_IID: i.i.d. cells take the collapsed household cycle and solve
+  int* out_iid;           // [n_cal] 1: the calibration's distribution solves ran on the asset grid
   int aa_period;          // EGM Anderson mixing every aa_period cycles (0: off; AIY_OPT_GE_ANDERSON)
   double* aah;            // [n_cal][kGeAaHist][S][n_a] the last kGeAaHist EGM outputs (c, own nodes)
   int logsec;             // log-secant bracketing (AIY_OPT_GE_LOGSEC, with loose bracketing)
@@ -268,7 +277,7 @@ __device__ __forceinline__ double ge_egm_cycle(int S, int n_a, int j0, int j1, c
                                                const double* src_m, const double* src_c, double* dst_m,
                                                double* dst_c, bool track, double R, double beta, double gam,
                                                const double* s_Wl, const double* s_Pe, int* s_hint,
-                                               double* lds_v, double* lds_win, double* ring) {
+                                               double* lds_v, double* lds_win, double* ring, bool iid) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
   const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
   const int n1 = n_a + 1;
@@ -285,11 +294,14 @@ __device__ __forceinline__ double ge_egm_cycle(int S, int n_a, int j0, int j1, c
         const double c = (R * a + s_Wl[sp]) * 1.0;
         Vw[sp * kTile + lane] = R * marg_u<PK>(c, gam);   // read back by the same lane only
       }
+      double c = 0.0;
       for (int s = 0; s < S; ++s) {
-        double sum;
-        if constexpr (SC > 0) sum = pairwise_dot<SC>(Vw + lane, s_Pe + s * SC);
-        else sum = np_pairwise_sum<SMAX>(S, [&](int t) { return Vw[t * kTile + lane] * uniform_f64(s_Pe[s * S + t]); });
-        const double c = inv_marg<PK>(beta * sum, gam);
+        if (s == 0 || !iid) {   // (i.i.d.: every state's expectation is state 0's, bit for bit)
+          double sum;
+          if constexpr (SC > 0) sum = pairwise_dot<SC>(Vw + lane, s_Pe + s * SC);
+          else sum = np_pairwise_sum<SMAX>(S, [&](int t) { return Vw[t * kTile + lane] * uniform_f64(s_Pe[s * S + t]); });
+          c = inv_marg<PK>(beta * sum, gam);
+        }
         store_f64_agent(&dst_m[(size_t)s * n1 + j + 1], a + c);
         store_f64_agent(&dst_c[(size_t)s * n1 + j + 1], c);
         if (ring) store_f64_agent(&ring[(size_t)s * n_a + j], c);
@@ -317,17 +329,23 @@ __device__ __forceinline__ double ge_egm_cycle(int S, int n_a, int j0, int j1, c
       pcv[s] = load_f64_agent(&src_c[(size_t)rr * n1 + j + 1]);
     }
   };
+  // i.i.d. income (iid, wave-uniform: every row of P the same bits): E[s] is the same number for
+  // every s, so the expectation and inv_marg run for s = 0 only and c, m are reused for s >= 1;
+  // the stores and the distance stay per state
   auto end = [&](int, int j, double a) {   // phase 2 (each lane reads its own V)
+    double c = 0.0, m = 0.0;
 #pragma unroll
     for (int s = 0; s < NP; ++s) {
       if (s < S) {
         __builtin_amdgcn_sched_barrier(0);   // one state's P reads at a time (no hoisting of all S x S)
-        double sum;
-        if constexpr (SC > 0) sum = pairwise_dot<SC>(Vw + lane, s_Pe + s * SC);
-        else sum = np_pairwise_sum<SMAX>(S, [&](int t) { return Vw[t * kTile + lane] * uniform_f64(s_Pe[s * S + t]); });
-        const double E = beta * sum;                     // EndOfPrdvP (AS:1485)
-        const double c = inv_marg<PK>(E, gam);           // AS:1490
-        const double m = a + c;                          // AS:1499
+        if (s == 0 || !iid) {
+          double sum;
+          if constexpr (SC > 0) sum = pairwise_dot<SC>(Vw + lane, s_Pe + s * SC);
+          else sum = np_pairwise_sum<SMAX>(S, [&](int t) { return Vw[t * kTile + lane] * uniform_f64(s_Pe[s * S + t]); });
+          const double E = beta * sum;                     // EndOfPrdvP (AS:1485)
+          c = inv_marg<PK>(E, gam);                        // AS:1490
+          m = a + c;                                       // AS:1499
+        }
         store_f64_agent(&dst_m[(size_t)s * n1 + j + 1], m);
         store_f64_agent(&dst_c[(size_t)s * n1 + j + 1], c);
         if (ring) store_f64_agent(&ring[(size_t)s * n_a + j], c);   // Anderson history (own nodes)
@@ -365,9 +383,9 @@ template <int SMAX, int SC, int PK, int NW>
 __device__ __forceinline__ double ge_egm_cycle_fn(int S, int n_a, int j0, int j1, const double* a_grid,
                                                const double* src_m, const double* src_c, double* dst_m,
                                                double* dst_c, bool track, double R, double beta, double gam,
-                                               double* dyn, double* ring) {
+                                               double* dyn, double* ring, bool iid) {
   return ge_egm_cycle<SMAX, SC, PK, NW>(S, n_a, j0, j1, a_grid, src_m, src_c, dst_m, dst_c, track, R, beta, gam,
-                                        ge_s_Wl, ge_s_Pe, ge_s_hint, dyn, dyn + (size_t)NW * SMAX * kTile, ring);
+                                        ge_s_Wl, ge_s_Pe, ge_s_hint, dyn, dyn + (size_t)NW * SMAX * kTile, ring, iid);
 }
 
 // lottery of the own columns on the final tables (hist.hip hist_lottery_kernel's arithmetic)
@@ -426,6 +444,7 @@ struct GeCtx {
   double beta, gam;
   size_t tab_sz;
   int j0, j1, w, G, S, n_a, cal, lc;
+  int iid;                // i.i.d. income (every row of P the same bits) with AIY_OPT_HIST_IID on
   __device__ __forceinline__ double* tabm(int b) const { return tab + (size_t)b * 2 * tab_sz; }
   __device__ __forceinline__ double* tabc(int b) const { return tab + (size_t)b * 2 * tab_sz + tab_sz; }
 };
@@ -607,7 +626,7 @@ __device__ __forceinline__ int ge_household_solve(const GeCtx& cx, unsigned& nb,
       const bool track = n >= 2;
       double* ring = aa && ge_ring_wanted(n, g.aa_period) ? ge_ring(cx, n) : nullptr;
       const double dl = ge_egm_cycle_fn<SMAX, SC, PK, NW>(cx.S, cx.n_a, cx.j0, cx.j1, cx.a_grid, sm, sc, cx.tabm(b_dst),
-                                                          cx.tabc(b_dst), track, R, cx.beta, cx.gam, dyn, ring);
+                                                          cx.tabc(b_dst), track, R, cx.beta, cx.gam, dyn, ring, cx.iid != 0);
       // cluster distance: the value itself at the extrapolation checks (cycles 32k - 1,
       // 32k), else only its two facts (some part > tol; some part NaN) on a counting barrier
       const int xp = g.extrap_period;
@@ -683,7 +702,7 @@ struct GeHhArgs {
   gptr<unsigned long long> gran;
   gptr<const double> a_grid, init_m, init_c;
   double beta, gam, R;
-  int j0, j1, w, G, S, n_a;
+  int j0, j1, w, G, S, n_a, iid;
   GeHhOpt opt;
   unsigned dyn_lds;   // hk_lds_addr(ge_dyn)
 };
@@ -705,6 +724,7 @@ __device__ __noinline__ int ge_household_isolated(GeHhArgs a, unsigned* nb_io, u
   cx.S = SC > 0 ? SC : hk_uni(a.S);
   cx.n_a = hk_uni(a.n_a);
   cx.cal = cx.lc = 0;
+  cx.iid = hk_uni(a.iid);
   cx.tab_sz = (size_t)cx.S * (cx.n_a + 1);
   const GeHhOpt opt = {hk_uni(a.opt.max_cyc), hk_uni(a.opt.aa_period), hk_uni(a.opt.extrap_period)};
   unsigned nb = *nb_io, ne = *ne_io;
@@ -833,6 +853,16 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
     st.nbc = 0u;
   }
   __syncthreads();
+  // i.i.d. income: S >= 2 and every row of P equal to row 0 bit for bit, compared as integers (one
+  // differing bit: the general path).  Every workgroup of the cluster reads the same bits of P, so
+  // the flag is cluster-uniform: all of them take the same barriers and reductions below.
+  {
+    int iid = g.iid_on != 0 && S >= 2;
+    for (int q = S; q < S * S; ++q)
+      iid &= __double_as_longlong(ge_s_Pe[q]) == __double_as_longlong(ge_s_Pe[q % S]);
+    cx.iid = __builtin_amdgcn_readfirstlane(iid);
+  }
+  if (w == 0 && tid == 0) g.out_iid[cal] = (!PULL && cx.iid) ? 1 : 0;
 
   bool stopped = false;
   while ((!st.ev.rs.done && st.ev.steps < g.max_steps) || st.ev.final_ks) {
@@ -878,7 +908,7 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
       ha.init_m = to_global((const double*)(secant ? cx.tabm(b_init) : (warm ? cx.tabm(b_cur) : nullptr)));
       ha.init_c = to_global((const double*)(secant ? cx.tabc(b_init) : (warm ? cx.tabc(b_cur) : nullptr)));
       ha.beta = cx.beta; ha.gam = cx.gam; ha.R = R;
-      ha.j0 = j0; ha.j1 = j1; ha.w = w; ha.G = G; ha.S = S; ha.n_a = n_a;
+      ha.j0 = j0; ha.j1 = j1; ha.w = w; ha.G = G; ha.S = S; ha.n_a = n_a; ha.iid = cx.iid;
       ha.opt = {g.max_cyc, g.aa_period, g.extrap_period};
       ha.dyn_lds = hk_lds_addr(ge_dyn);
       // one instantiation per CRRA kind (1, 3, 5, else the general pow), each with one copy of the cycle
@@ -932,6 +962,8 @@ __global__ __launch_bounds__(TH) void ge_cluster_kernel(GeRun g) {
       hk.lottery_fresh = true;
       hk.dyn_lds = hk_lds_addr(ge_dyn);
       if constexpr (PULL) mv = hk_solve_inlined<SMAX, KC, TH, true, false, SC>(hk, &nb, &ne);
+      else if (cx.iid)   // (cluster-uniform) the asset-grid solve, a function of its own
+        mv = hk_solve_isolated<SMAX, KC, TH, false, (KC == 1 || kGeIidFuseAKc2) && kGeFuseA, SC, true>(hk, &nb, &ne);
       else mv = hk_solve_isolated<SMAX, KC, TH, false, (KC == 1 || kGeFuseAKc2) && kGeFuseA, SC>(hk, &nb, &ne);
     }
     if (mv == -1) return;
@@ -1042,7 +1074,7 @@ static bool ge_make_plan(aiy_handle* h, int n_cal, int S, int n_a, GePlan& p) {
 // capacity (cap_max doubles).
 struct GeScratch {
   double *tab, *mass, *pmass, *pg, *qb, *wlo, *slab, *outd, *prof, *evlog, *aah;
-  int *ainv, *lo, *span, *ids, *resume, *done, *outi;
+  int *ainv, *lo, *span, *ids, *resume, *done, *outi, *iid;
   unsigned *ctr, *err;
   unsigned long long* gran;
   GeState* saved;
@@ -1071,6 +1103,7 @@ static GeScratch ge_scratch(Carve c, int n_cal, int S, int n_a, int cus, int cap
   L.prof = c.take<double>((size_t)n_cal * kGeProf);
   L.evlog = c.take<double>((size_t)n_cal * kGeEvLog * kGeEvRec);
   L.aah = c.take<double>((size_t)n_cal * kGeAaHist * S * n_a);
+  L.iid = c.take<int>(n_cal);
   L.bytes = c.bytes();
   return L;
 }
@@ -1084,6 +1117,7 @@ static GeScratch ge_scratch(Carve c, int n_cal, int S, int n_a, int cus, int cap
 int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, const aiy_ge_options* o, double* r_out,
                                double* K_out, double* Ks_out, int32_t* steps_out, int32_t* cyc_out,
                                int32_t* its_out, int32_t* status_out, hipStream_t st) {
+  h->ge_iid_cells = 0;   // (also when the host-driven loop runs instead: it has no reduced solve)
   if (!h->ge_resident || o->accel >= 0) return 0;   // BiCGSTAB distribution solves only
   const int n_cal = M->n_cal, S = M->S, n_a = M->n_a;
   GePlan p0;
@@ -1116,6 +1150,7 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
   g.extrap_period = h->ge_extrap_period;
   g.aa_period = o->egm_extrapolate != 0 ? h->ge_anderson : 0;   // (with the EGM acceleration on)
   g.aah = L.aah;
+  g.iid_on = h->hist_iid; g.out_iid = L.iid;
   g.logsec = h->ge_logsec;
   g.tab = L.tab; g.mass = L.mass; g.pmass = L.pmass; g.pg = L.pg; g.qb = L.qb; g.ainv = L.ainv;
   g.loose_hist = std::pow(10.0, -(double)h->ge_loose_hist);
@@ -1183,7 +1218,8 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
     active.swap(next);
   }
   std::vector<double> hd(3 * (size_t)n_cal);
-  std::vector<int> hi(4 * (size_t)n_cal);
+  std::vector<int> hi(4 * (size_t)n_cal), iid_h(n_cal, 0);
+  AIY_HIP(h, hipMemcpyAsync(iid_h.data(), L.iid, sizeof(int) * n_cal, hipMemcpyDeviceToHost, st));
   AIY_HIP(h, hipMemcpyAsync(hd.data(), outd, sizeof(double) * 3 * n_cal, hipMemcpyDeviceToHost, st));
   AIY_HIP(h, hipMemcpyAsync(hi.data(), outi, sizeof(int) * 4 * n_cal, hipMemcpyDeviceToHost, st));
   h->ge_prof.assign((size_t)n_cal * kGeProf, 0.0);
@@ -1196,6 +1232,7 @@ int32_t ge_stationary_resident(aiy_handle* h, const aiy_stationary_model* M, con
   long long cyc = 0, its = 0;
   int steps = 0;
   for (int c = 0; c < n_cal; ++c) {
+    h->ge_iid_cells += iid_h[c] != 0;
     r_out[c] = hd[c];
     K_out[c] = hd[n_cal + c];
     if (Ks_out) Ks_out[c] = hd[2 * n_cal + c];
@@ -1236,6 +1273,15 @@ extern "C" int32_t aiy_ge_last_rounds(aiy_handle* h, int32_t* launches, int32_t*
   if (!h) return AIY_ERR_ARG;
   if (launches) *launches = h->ge_rounds;
   if (mid_solve_stops) *mid_solve_stops = h->ge_mid_stops;
+  return AIY_OK;
+}
+
+// Calibrations of the last aiy_ge_stationary call whose distribution solves ran on the asset grid
+// alone (i.i.d. income, AIY_OPT_HIST_IID on, the push form of the device-resident search): the flag
+// each cluster's kernel set from the P it read; 0 after a host-driven search.  Host-only.
+extern "C" int32_t aiy_ge_last_iid_cells(aiy_handle* h, int32_t* cells) {
+  if (!h || !cells) return AIY_ERR_ARG;
+  *cells = h->ge_iid_cells;
   return AIY_OK;
 }
 

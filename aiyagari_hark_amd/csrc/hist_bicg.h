@@ -69,9 +69,20 @@ __device__ __forceinline__ double hk_rhat(unsigned q) {
       tq = tn;                                                          \
     }                                                                   \
   } while (0)
+#define HK_PH_REPORT(mv)                                                                                           \
+  do {                                                                                                             \
+    if (tid == 0 && blockIdx.x >= AIY_DIAG_PHASES && blockIdx.x < AIY_DIAG_PHASES + 10 && (mv) > 0)                \
+      printf("[bicg phases] block %d G=%d nj=%d matvecs=%d us/matvec: push %.2f publish %.2f barrier %.2f "        \
+             "gather+mix %.2f reduce %.2f vector %.2f\n",                                                          \
+             (int)blockIdx.x, G, j1 - j0, (mv), ph[0] * 0.01 / (mv), ph[1] * 0.01 / (mv), ph[2] * 0.01 / (mv),     \
+             ph[3] * 0.01 / (mv), ph[4] * 0.01 / (mv), ph[5] * 0.01 / (mv));                                       \
+  } while (0)
 #else
 #define HK_PH(k) \
   do {           \
+  } while (0)
+#define HK_PH_REPORT(mv) \
+  do {                   \
   } while (0)
 #endif
 
@@ -148,10 +159,22 @@ __device__ __forceinline__ unsigned hk_lds_addr(double* p) {
 // a rebalancing stop was requested (X holds the current iterate; a later solve restarts
 // from it).  nb / ne: the
 // cluster barriers / reductions passed so far in this launch (counted on).
-template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false, int SC = 0>
+//
+// IID (push form): the calibration's income is i.i.d. -- every row of P is the same vector pi, bit
+// for bit (the caller's test) -- so T x = pi (x) (M mu) for any x, with mu[j] = sum_s x[s][j] and
+// M = sum_s pi_s Push_s on the asset grid alone.  The solve then runs on mu: ONE unknown per column
+// instead of S.  The lottery push, the spans, the publish and the cluster exchange are the general
+// form's (state s pushes pi_s mu[j]); the gather sums the states (no P mix); r, p, v, t, x and u of
+// a column stay in registers at one and at two columns per thread (no Pg / X traffic inside the
+// loop, no v in LDS), and so does its lottery.  X is the interface as before: in, the start, read
+// as mu0[j] = sum_s X[s][j]; out, pi_s (M mu)[j], also at a rebalancing stop (pi_s mu[j]).  The loop
+// runs at tol / max_s pi_s: max|M mu - mu| max pi < tol is the full vector's max|T x - x| < tol.
+template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false, int SC = 0, bool IID = false>
 __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC, TH>& L, unsigned& nb,
                                         unsigned& ne) {
   constexpr bool kVlds = SMAX <= 8;
+  static_assert(!IID || (!PULL && SMAX <= 8), "the asset-grid solve: push form, S <= 8");
+  constexpr int NV = IID ? 1 : SMAX;   // unknowns per column
 #ifdef AIY_DIAG_PHASES
   unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, tq = 0;
 #endif
@@ -338,7 +361,8 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   }
   // lottery in registers with one column per thread at <= 8 waves (256 VGPRs); with two columns
   // per thread, or 16 waves (128 VGPRs), the registers hold the Krylov vectors
-  constexpr bool kLoReg = SMAX <= 8 && KC == 1 && TH <= 512;
+  // (the asset-grid solve: always, its vectors are one value per column)
+  constexpr bool kLoReg = SMAX <= 8 && (KC == 1 || IID) && TH <= 512;
   int dreg[KC][kLoReg ? SMAX : 1];
   double wreg[KC][kLoReg ? SMAX : 1];
   if constexpr (kLoReg) {
@@ -356,6 +380,12 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   const int v_base = lane < S ? s_base[lane] : 0;
   const int v_plo = lane < 2 * S ? s_pub[lane][0] : 0;
   const int v_phi = lane < 2 * S ? s_pub[lane][1] : 0;
+  // IID: pi = P's (common) row in SGPRs
+  double pi[IID ? SMAX : 1];
+  if constexpr (IID) {
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) pi[s] = hk_uni(s_P[s]);
+  }
   // the column index is re-materialised per phase through an empty asm: otherwise the
   // compiler hoists every point's address, hash and predicate out of the loop and keeps
   // them live across the gathers (hundreds of VGPRs of spills)
@@ -368,7 +398,7 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
 
   // ---- the matvec pieces ----
   // push q's own sources into the LDS spans (np.add.at(T[s], lo, wlo q) and lo + 1)
-  auto push = [&](const double (&q)[KC][SMAX]) {
+  auto push = [&](const double (&q)[KC][NV]) {
     // lottery rows in groups whose loads (L2) are all in flight before the first atomic
     constexpr int PR = SMAX <= 8 ? SMAX : 4;
     const int jc = col();   // lottery addresses formed here, not hoisted (they spilled)
@@ -405,8 +435,11 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
             const int s = s0 + u;
             if (s < S) {   // wave-uniform
               const int d = dd[k][u];
-              const double vlo = ww[k][u] * q[k][s];          // np.add.at(T[s], lo, wlo q)
-              const double vhi = (1.0 - ww[k][u]) * q[k][s];  // np.add.at(T[s], lo + 1, (1 - wlo) q)
+              double qs;
+              if constexpr (IID) qs = pi[s] * q[k][0];        // state s's share of the column's mass
+              else qs = q[k][s];
+              const double vlo = ww[k][u] * qs;          // np.add.at(T[s], lo, wlo q)
+              const double vhi = (1.0 - ww[k][u]) * qs;  // np.add.at(T[s], lo + 1, (1 - wlo) q)
               const int ilo = __builtin_amdgcn_readlane(v_base, s) + d, ihi = ilo + 1;
               const int d0 = __builtin_amdgcn_readfirstlane(d);
               if (__all(act && d == d0)) {   // the whole wave on one destination (borrowing constraint)
@@ -440,7 +473,8 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   };
   // gather the own destinations (ascending covering workgroup) and mix: Tq[k][s'] =
   // sum_s P[s, s'] T_s[d]
-  auto gather_mix = [&](int par, double (&out)[KC][SMAX]) {
+  // (IID: out[k][0] = sum_s T_s[d], s ascending, no mix)
+  auto gather_mix = [&](int par, double (&out)[KC][NV]) {
     constexpr int GR = 4;
     double T[KC][SMAX];
 #pragma unroll
@@ -565,6 +599,15 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
         }
       }
     }
+    if constexpr (IID) {
+#pragma unroll
+      for (int k = 0; k < KC; ++k) {
+        double acc = T[k][0];
+#pragma unroll
+        for (int s = 1; s < SMAX; ++s) acc += T[k][s];   // (rows past S are 0.0)
+        out[k][0] = acc;
+      }
+    } else {
 #pragma unroll
     for (int sp = 0; sp < SMAX; ++sp) {
       double pc[SMAX];
@@ -579,6 +622,7 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
         out[k][sp] = acc;
       }
     }
+    }   // !IID
   };
   // pull form: q of the own points staged in Qg (the exported entries write-through), one
   // cluster barrier, then every own destination pulls its sources (hist_pull.h)
@@ -681,7 +725,7 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     }
   };
   // one matvec: out = T q (the cluster exchange in the middle)
-  auto matvec = [&](const double (&q)[KC][SMAX], double (&out)[KC][SMAX]) -> bool {
+  auto matvec = [&](const double (&q)[KC][NV], double (&out)[KC][NV]) -> bool {
     if constexpr (PULL) {
       HK_PH(5);
       stage_q(q);
@@ -727,7 +771,7 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
   // so every workgroup's are in memory once the barrier has passed; the last wave reads them
   // while the other waves gather, and s_res is valid on return
   // do_push(): the push of the matvec input (ends with a workgroup barrier)
-  auto matvec_rp = [&](auto&& do_push, double (&out)[KC][SMAX], const double* vals, int nv, unsigned kmax) -> bool {
+  auto matvec_rp = [&](auto&& do_push, double (&out)[KC][NV], const double* vals, int nv, unsigned kmax) -> bool {
     HK_PH(5);
     hc_wave_parts(vals, nv, kmax, s_part);
     do_push();   // ends with a workgroup barrier: s_part complete
@@ -749,9 +793,230 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     HK_PH(3);
     return *L.s_rok != 0;
   };
-  auto matvec_r = [&](const double (&q)[KC][SMAX], double (&out)[KC][SMAX], const double* vals, int nv,
+  auto matvec_r = [&](const double (&q)[KC][NV], double (&out)[KC][NV], const double* vals, int nv,
                       unsigned kmax) -> bool { return matvec_rp([&] { push(q); }, out, vals, nv, kmax); };
+  if constexpr (IID) {
+    int mv = 0;                 // matvecs
+    auto col_act = [&](int jc, bool (&act)[KC]) {   // (as the general loop's below)
+#pragma unroll
+      for (int k = 0; k < KC; ++k) act[k] = jc + k * TH < j1;
+    };
+    // ---- BiCGSTAB on (I - M) mu = 0: the general loop below with one unknown per column, every
+    //      vector in registers; the same stopping, stall, restart and breakdown rules ----
+    // TWIN of the general loop: the stop poll, the convergence / max_iter tests, the stall rule
+    // (kHkStall, 0.9 best), the breakdown tests on alpha, omega, beta and rho and the rescale to the
+    // start's total are copied from it line for line.  A change to any of them there is made here
+    // too (tests/test_gpu_iid_cells.py holds the two to each other only within the search bounds).
+    double pimax = 0.0;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s)
+      if (s < S) pimax = fmax(pimax, pi[s]);
+    const double tol = r.tol / pimax;
+    double xv[KC][1], rv[KC][1], pv[KC][1], tv[KC][1], vv[KC], uv[KC];
+    double part[kHcRed];
+    bool restart = true, first = true;
+    double rho = 0.0, total0 = 0.0;
+    bool act[KC];
+    double pu = 0.0;   // FUSEA: this thread's part of <u, p>
+    unsigned seed = 0;
+    auto rh_at = [&](int jc, int k) { return hk_rhat((unsigned)(jc + k * TH) + seed * 0x5BD1E995u); };
+    double best = __builtin_inf();
+    int mv_best = 0;
+    // X[s][j] = pi_s m[j] of the own columns
+    auto store_x = [&](int jc, const double (&m)[KC]) {
+#pragma unroll
+      for (int k = 0; k < KC; ++k)
+        if (jc + k * TH < j1) {
+#pragma unroll
+          for (int s = 0; s < SMAX; ++s)
+            if (s < S) X[(size_t)s * n_a + jc + k * TH] = pi[s] * m[k];
+        }
+    };
+    {   // mu0[j] = sum_s X[s][j], s ascending
+      const int jc = col();
+#pragma unroll
+      for (int k = 0; k < KC; ++k) {
+        double xs[SMAX];
+#pragma unroll
+        for (int s = 0; s < SMAX; ++s) xs[s] = X[min(s, S - 1) * n_a + min(jc + k * TH, n_a - 1)];
+        double acc = xs[0];
+#pragma unroll
+        for (int s = 1; s < SMAX; ++s)
+          if (s < S) acc += xs[s];
+        xv[k][0] = jc + k * TH < j1 ? acc : 0.0;
+      }
+    }
+    HK_PH(-1);
+    while (true) {
+      if (restart) {
+        // true residual of mu: tv = M mu, rv = M mu - mu
+        if (!matvec(xv, tv)) return -1;
+        ++mv;
+        const int jc = col();
+        col_act(jc, act);
+        double rr = 0.0, rm = 0.0, xs = 0.0;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+          rv[k][0] = tv[k][0] - xv[k][0];
+          if (act[k]) {
+            rr += rh_at(jc, k) * rv[k][0];
+            rm = nan_max(rm, fabs(rv[k][0]));
+            xs += xv[k][0];
+          }
+        }
+        part[0] = rr;
+        part[1] = rm;
+        part[2] = xs;
+        if (!reduce(part, 3, 2u, [] {})) return -1;
+        rho = s_res[0];
+        if (mv == 1) total0 = s_res[2];   // the starting mass's total
+        if (s_res[1] < tol || mv >= r.max_iter) {   // converged: pi (x) M mu, rescaled to the start's total
+          const double scale = total0 / s_res[2];
+          double m[KC];
+#pragma unroll
+          for (int k = 0; k < KC; ++k) m[k] = mv == 1 ? tv[k][0] : tv[k][0] * scale;
+          store_x(jc, m);
+          break;
+        }
+        double pun = 0.0;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+          pv[k][0] = rv[k][0];
+          uv[k] = 0.0;
+          if constexpr (FUSEA) {   // u = rh - M^T rh of the own columns (their own lottery only)
+            if (act[k]) {
+              double tr = 0.0;
+#pragma unroll
+              for (int s = 0; s < SMAX; ++s)
+                if (s < S) {
+                  const unsigned q = (unsigned)dreg[k][s] + seed * 0x5BD1E995u;
+                  tr += pi[s] * (wreg[k][s] * hk_rhat(q) + (1.0 - wreg[k][s]) * hk_rhat(q + 1u));
+                }
+              uv[k] = rh_at(jc, k) - tr;
+              pun += uv[k] * pv[k][0];
+            }
+          }
+        }
+        pu = pun;
+        restart = false;
+        first = true;
+      }
+      // rebalancing stop request, polled every 8th iteration (see the general loop)
+      if (r.stop_ctr != nullptr && tid == 0 && ((mv >> 1) & 7) == 0)
+        s_stop = __hip_atomic_load((const unsigned*)r.stop_ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= r.stop_at;
+      int jc = col();
+      col_act(jc, act);
+      if constexpr (FUSEA) {   // <u, p> = <rh, v> and max|r| ride on the matvec's barrier
+        double rm = 0.0;
+#pragma unroll
+        for (int k = 0; k < KC; ++k)
+          if (act[k]) rm = nan_max(rm, fabs(rv[k][0]));
+        part[0] = pu;
+        part[1] = (r.stop_ctr != nullptr && tid == 0 && s_stop) ? kHkStopSentinel : rm;
+        if (!matvec_r(pv, tv, part, 2, 2u)) return -1;
+        ++mv;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) vv[k] = pv[k][0] - tv[k][0];
+      } else {
+        if (!matvec(pv, tv)) return -1;
+        ++mv;
+        jc = col();
+        col_act(jc, act);
+        double rvv = 0.0, rm = 0.0;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+          vv[k] = pv[k][0] - tv[k][0];
+          if (act[k]) {
+            rvv += rh_at(jc, k) * vv[k];
+            rm = nan_max(rm, fabs(rv[k][0]));
+          }
+        }
+        part[0] = rvv;
+        part[1] = (r.stop_ctr != nullptr && tid == 0 && s_stop) ? kHkStopSentinel : rm;
+        if (!reduce(part, 2, 2u, [] {})) return -1;
+      }
+      if (s_res[1] >= kHkStopSentinel) {   // every workgroup reads the same max: X = pi (x) mu, a valid iterate
+        double m[KC];
+#pragma unroll
+        for (int k = 0; k < KC; ++k) m[k] = xv[k][0];
+        store_x(col(), m);
+        return -(2 + mv);
+      }
+      if ((!first && s_res[1] < tol) || mv >= r.max_iter) {   // recursive residual converged: verify
+        restart = true;
+        continue;
+      }
+      if (first || s_res[1] < 0.9 * best) {
+        best = first ? __builtin_inf() : s_res[1];
+        mv_best = mv;
+      } else if (mv - mv_best > kHkStall) {   // stagnation: the next shadow residual
+        ++seed;
+        best = __builtin_inf();
+        restart = true;
+        continue;
+      }
+      first = false;
+      const double alpha = rho / s_res[0];
+      if (!(fabs(alpha) < 1e300)) {   // breakdown or NaN: restart from the true residual
+        restart = true;
+        continue;
+      }
+      // x += alpha p; s = r - alpha v (in rv); t = s - M s (in tv)
+#pragma unroll
+      for (int k = 0; k < KC; ++k) {
+        xv[k][0] += alpha * pv[k][0];
+        rv[k][0] -= alpha * vv[k];
+      }
+      if (!matvec(rv, tv)) return -1;
+      ++mv;
+      jc = col();
+      col_act(jc, act);
+      double ts = 0.0, tt = 0.0, rs = 0.0, rt = 0.0, sm = 0.0;
+#pragma unroll
+      for (int k = 0; k < KC; ++k) {
+        tv[k][0] = rv[k][0] - tv[k][0];
+        if (act[k]) {
+          const double h = rh_at(jc, k);
+          ts += tv[k][0] * rv[k][0];
+          tt += tv[k][0] * tv[k][0];
+          rs += h * rv[k][0];
+          rt += h * tv[k][0];
+          sm = nan_max(sm, fabs(rv[k][0]));
+        }
+      }
+      part[0] = ts;
+      part[1] = tt;
+      part[2] = rs;
+      part[3] = rt;
+      part[4] = sm;
+      if (!reduce(part, 5, 16u, [] {})) return -1;
+      double omega = (s_res[4] < tol) ? 0.0 : s_res[0] / s_res[1];
+      if (!(fabs(omega) < 1e300)) omega = 0.0;
+      if (omega == 0.0) {   // s already below tol (x + alpha p is the answer), or <t, t> = 0: verify
+        restart = true;
+        continue;
+      }
+      const double rho2 = s_res[2] - omega * s_res[3];
+      const double beta = (rho2 / rho) * (alpha / omega);
+      rho = rho2;
+      // x += omega s; r = s - omega t; p = r + beta (p - omega v)
+      double pun = 0.0;
+#pragma unroll
+      for (int k = 0; k < KC; ++k) {
+        xv[k][0] += omega * rv[k][0];
+        rv[k][0] = rv[k][0] - omega * tv[k][0];
+        pv[k][0] = rv[k][0] + beta * (pv[k][0] - omega * vv[k]);
+        if constexpr (FUSEA) pun += uv[k] * pv[k][0];
+      }
+      pu = pun;
+      if (!(fabs(beta) < 1e300) || rho == 0.0) restart = true;
+    }
+    HK_PH_REPORT(mv);
+    return mv;
+  } else {
   // ---- BiCGSTAB ----
+  // (TWIN: the IID block above repeats this loop's stop poll, convergence, stall, breakdown and
+  // rescale rules for one unknown per column; change them in both places)
   // registers: r (then s), p, and the matvec result; v waits in LDS (behind the spans) and
   // p in the HBM scratch row across the second matvec, whose gather needs the registers
   double rv[KC][SMAX], pv[KC][SMAX], tv[KC][SMAX];
@@ -1092,14 +1357,9 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     pu = pun;
     if (!(fabs(beta) < 1e300) || rho == 0.0) restart = true;
   }
-#ifdef AIY_DIAG_PHASES
-  if (tid == 0 && blockIdx.x >= AIY_DIAG_PHASES && blockIdx.x < AIY_DIAG_PHASES + 10 && mv > 0)
-    printf("[bicg phases] block %d G=%d nj=%d matvecs=%d us/matvec: push %.2f publish %.2f barrier %.2f gather+mix "
-           "%.2f reduce %.2f vector %.2f\n",
-           (int)blockIdx.x, G, j1 - j0, mv, ph[0] * 0.01 / mv, ph[1] * 0.01 / mv, ph[2] * 0.01 / mv, ph[3] * 0.01 / mv,
-           ph[4] * 0.01 / mv, ph[5] * 0.01 / mv);
-#endif
+  HK_PH_REPORT(mv);
   return mv;
+  }   // !IID
 }
 
 // The arguments of a non-kernel function arrive in VGPRs, where the compiler must take them for
@@ -1137,7 +1397,29 @@ __device__ __forceinline__ HkArgs hk_uniform_args(const HkArgs& a) {
 // carries a lot of live state of its own (ge_resident.hip's search loop) would otherwise
 // force the solve's registers into scratch; the call costs a few register saves per
 // solve.  The span buffer / v share the caller's dynamic LDS (HkArgs::dyn_lds).
-template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false, int SC = 0>
+// Its LDS arrays are one object per (SMAX, KC, TH): the general and the asset-grid (IID) solve of
+// one kernel are two functions, each with its own register allocation, that never run at the
+// same time and share it (declared inside, each brought its own: +20 KB at two columns per
+// thread, taken from the span buffer).
+template <int SMAX, int KC, int TH>
+struct HkIsoLds {
+  int s_base[SMAX];
+  int s_pub[2 * SMAX][2];
+  int s_tot;
+  HcCand s_cand[SMAX][kHcCand];
+  int s_ncand[SMAX];
+  unsigned short s_cinfo[KC * SMAX * TH];
+  double s_P[SMAX * SMAX];
+  double s_part[kHcRed][TH / kWave];
+  double s_res[kHcRed];
+  int s_flag, s_stop;
+  int s_ex[2 * SMAX];
+  int s_nheavy, s_heavy[kHkHeavy][4], s_rok, s_wcnt[TH / kWave];
+  double s_hval[kHkHeavy];
+};
+template <int SMAX, int KC, int TH>
+__shared__ HkIsoLds<SMAX, KC, TH> hk_iso_lds;
+template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false, int SC = 0, bool IID = false>
 __device__ __noinline__ int hk_solve_isolated(HkArgs a, unsigned* nb_io, unsigned* ne_io);
 // the same body inlined into the caller (the pull form spilled more as a separate function)
 template <int SMAX, int KC, int TH, bool PULL = false, bool FUSEA = false, int SC = 0>
@@ -1164,28 +1446,17 @@ __device__ __forceinline__ int hk_solve_inlined(HkArgs a, unsigned* nb_io, unsig
   *ne_io = ne;
   return mv;
 }
-template <int SMAX, int KC, int TH, bool PULL, bool FUSEA, int SC>
+template <int SMAX, int KC, int TH, bool PULL, bool FUSEA, int SC, bool IID>
 __device__ __noinline__ int hk_solve_isolated(HkArgs a, unsigned* nb_io, unsigned* ne_io) {
   // the caller's dynamic LDS by address (wave-uniform, one SGPR), typed LDS so that every access
   // stays a ds_ instruction
   double* hk_dyn = (double*)(lptr<double>)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)a.dyn_lds);
-  __shared__ int s_base[SMAX];
-  __shared__ int s_pub[2 * SMAX][2];
-  __shared__ int s_tot;
-  __shared__ HcCand s_cand[SMAX][kHcCand];
-  __shared__ int s_ncand[SMAX];
-  __shared__ unsigned short s_cinfo[KC * SMAX * TH];
-  __shared__ double s_P[SMAX * SMAX];
-  __shared__ double s_part[kHcRed][TH / kWave];
-  __shared__ double s_res[kHcRed];
-  __shared__ int s_flag, s_stop;
-  __shared__ int s_ex[2 * SMAX];
-  __shared__ int s_nheavy, s_heavy[kHkHeavy][4], s_rok, s_wcnt[TH / kWave];
-  __shared__ double s_hval[kHkHeavy];
-  HkShared<SMAX, KC, TH> L{hk_dyn, s_base, s_pub, &s_tot, s_cand, s_ncand, s_cinfo, s_P, s_part, s_res,
-                                 &s_flag, &s_stop, s_ex, &s_nheavy, s_wcnt, s_heavy, s_hval, &s_rok};
+  HkIsoLds<SMAX, KC, TH>& S_ = hk_iso_lds<SMAX, KC, TH>;
+  HkShared<SMAX, KC, TH> L{hk_dyn, S_.s_base, S_.s_pub, &S_.s_tot, S_.s_cand, S_.s_ncand, S_.s_cinfo, S_.s_P,
+                           S_.s_part, S_.s_res, &S_.s_flag, &S_.s_stop, S_.s_ex, &S_.s_nheavy, S_.s_wcnt,
+                           S_.s_heavy, S_.s_hval, &S_.s_rok};
   unsigned nb = *nb_io, ne = *ne_io;
-  const int mv = hk_solve<SMAX, KC, TH, PULL, FUSEA, SC>(hk_uniform_args(a), L, nb, ne);
+  const int mv = hk_solve<SMAX, KC, TH, PULL, FUSEA, SC, IID>(hk_uniform_args(a), L, nb, ne);
   *nb_io = nb;
   *ne_io = ne;
   return mv;

@@ -40,6 +40,7 @@ struct aiy_handle {
   int hist_krylov = 0;               // AIY_OPT_HIST_KRYLOV: resident histogram solves by BiCGSTAB
   int res_shape_stream = 1;          // AIY_OPT_RESIDENT_SHAPE_STREAM: shape of the HBM-streaming form (-1: res_shape)
   int hist_pull = 0;                 // AIY_OPT_HIST_PULL: BiCGSTAB matvecs of S <= 8 by the lottery pull
+  int hist_iid = 1;                  // AIY_OPT_HIST_IID: i.i.d.-income cells of the resident search collapse the income dimension
   int ge_loose_hist = 8;             // AIY_OPT_GE_LOOSE_HIST: loose-bracketing histogram tolerance 10^-value
   // per-calibration tolerances for one call (aiy_ge_stationary's loose bracketing); null: the
   // scalar tolerance of the call.  Device arrays [n_cal]; egm_tolh: the host copy.
@@ -57,6 +58,7 @@ struct aiy_handle {
   int ge_rebalance = 55;             // AIY_OPT_GE_REBALANCE: % finished that stops a launch (0: one launch)
   int ge_rounds = 0;                 // launches of the last device-resident search
   int ge_mid_stops = 0;              // of its clusters, those stopped inside a distribution solve
+  int ge_iid_cells = 0;              // of its calibrations, those whose distribution solves ran on the asset grid
   int ge_extrap_period = 32;         // AIY_OPT_GE_EXTRAP_PERIOD: EGM cycles between extrapolation checks
   int ge_anderson = 12;              // AIY_OPT_GE_ANDERSON: EGM cycles between Anderson mixes (0: off)
   int ge_logsec = 2;                 // AIY_OPT_GE_LOGSEC: 0 off, 1 two-point log-secant bracketing, 2 also from one point (with loose bracketing)

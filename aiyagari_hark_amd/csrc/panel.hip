@@ -493,6 +493,7 @@ extern "C" int32_t aiy_set_option(aiy_handle* h, int32_t option, int64_t value) 
       return AIY_OK;
     case AIY_OPT_HIST_KRYLOV: h->hist_krylov = value != 0; return AIY_OK;
     case AIY_OPT_HIST_PULL: h->hist_pull = value != 0; return AIY_OK;
+    case AIY_OPT_HIST_IID: h->hist_iid = value != 0; return AIY_OK;
     case AIY_OPT_RESIDENT_SHAPE_STREAM:
       if (value < -1 || value > 2) return fail(h, AIY_ERR_ARG, "AIY_OPT_RESIDENT_SHAPE_STREAM must be -1, 0, 1 or 2");
       h->res_shape_stream = (int)value;
@@ -545,6 +546,7 @@ extern "C" int32_t aiy_get_option(aiy_handle* h, int32_t option, int64_t* value)
     case AIY_OPT_HIST_ACCEL: *value = h->hist_accel; return AIY_OK;
     case AIY_OPT_HIST_KRYLOV: *value = h->hist_krylov; return AIY_OK;
     case AIY_OPT_HIST_PULL: *value = h->hist_pull; return AIY_OK;
+    case AIY_OPT_HIST_IID: *value = h->hist_iid; return AIY_OK;
     case AIY_OPT_RESIDENT_SHAPE_STREAM: *value = h->res_shape_stream; return AIY_OK;
     case AIY_OPT_GE_LOOSE_HIST: *value = h->ge_loose_hist; return AIY_OK;
     case AIY_OPT_GE_RESIDENT: *value = h->ge_resident; return AIY_OK;

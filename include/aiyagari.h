@@ -389,6 +389,16 @@ int32_t aiy_sim_block_periods(aiy_handle* h, const aiy_panel_batch* model, const
 #define AIY_OPT_RESIDENT_SHAPE_STREAM 18 /* workgroup shape (AIY_OPT_RESIDENT_SHAPE's values) of the resident
                                     panel's HBM-streaming form (agents beyond LDS, e.g. configs[3]);
                                     default 1 (1024 threads x 4 agents); -1: AIY_OPT_RESIDENT_SHAPE */
+#define AIY_OPT_HIST_IID 24        /* value != 0 (default 1): in the device-resident GE search a calibration
+                                    whose income is i.i.d. -- S >= 2 and every row of its P equal to
+                                    row 0 bit for bit, decided on the device from P itself -- runs
+                                    the expectation and inverse marginal utility of an EGM cycle
+                                    for one state instead of S (exact: the same bits), and, in the
+                                    push form, solves its distribution on the asset grid alone
+                                    (mu = M mu, M = sum_s pi_s Push_s; the mass is pi (x) mu; the
+                                    same stopping rule, max|T x - x| < tol).  0: such cells run the
+                                    general code.  With AIY_OPT_HIST_PULL every cell keeps the
+                                    general (bit-reproducible) distribution solve */
 /* (options 16, 19, 20, 21 and 22 -- fused panel draws, the 25-state resident search, the
    loader-ring panel, loose Brent evaluations, the on-chip S > 8 solve -- were measured slower
    than the defaults and removed in round 5; setting them returns AIY_ERR_ARG) */
@@ -519,6 +529,10 @@ int32_t aiy_ge_last_eval_log(aiy_handle* h, double* out, int32_t n_cal);
  * cluster stops happened inside a distribution solve (that solve resumes from its iterate in
  * the next launch).  Host-only. */
 int32_t aiy_ge_last_rounds(aiy_handle* h, int32_t* launches, int32_t* mid_solve_stops);
+/* Calibrations of the last aiy_ge_stationary call whose distribution solves ran on the asset
+ * grid alone (AIY_OPT_HIST_IID; each cluster of the device-resident search reports what it
+ * decided from its P); 0 when that call ran the host-driven loop.  Host-only. */
+int32_t aiy_ge_last_iid_cells(aiy_handle* h, int32_t* cells);
 
 /* Resident-histogram launch statistics (measurement hook): kernel milliseconds summed over
  * the device-resident distribution-iteration launches since the last reset (HIP events on

@@ -32,6 +32,7 @@ def main():
     ap.add_argument("--extrap", type=int, default=-1, help="AIY_OPT_GE_EXTRAP_PERIOD (-1: default)")
     ap.add_argument("--logsec", type=int, default=-1, help="AIY_OPT_GE_LOGSEC (-1: default)")
     ap.add_argument("--loose-hist", type=int, default=-1, help="AIY_OPT_GE_LOOSE_HIST (-1: default)")
+    ap.add_argument("--hist-iid", type=int, default=-1, help="AIY_OPT_HIST_IID (-1: default)")
     ap.add_argument("--stress", action="store_true", help="configs[4]'s 3 cells (25 states) instead of Table II")
     ap.add_argument("--all-evals", action="store_true", help="print every calibration's evaluation log")
     args = ap.parse_args()
@@ -54,8 +55,15 @@ def main():
         h.check(h.lib.aiy_set_option(h.h, _lib.AIY_OPT_GE_LOGSEC, args.logsec), "opt")
     if args.loose_hist >= 0:
         h.check(h.lib.aiy_set_option(h.h, _lib.AIY_OPT_GE_LOOSE_HIST, args.loose_hist), "opt")
+    if args.hist_iid >= 0:
+        h.check(h.lib.aiy_set_option(h.h, _lib.AIY_OPT_HIST_IID, args.hist_iid), "opt")
     if args.extrap >= 0:
         h.check(h.lib.aiy_set_option(h.h, _lib.AIY_OPT_GE_EXTRAP_PERIOD, args.extrap), "opt")
+    # i.i.d. cells (every row of P the same bits): the cells AIY_OPT_HIST_IID collapses
+    def rows_equal(P):
+        B = np.ascontiguousarray(P, dtype=np.float64).view(np.int64)
+        return B.shape[0] >= 2 and bool(np.all(B == B[0]))
+    iid = [rows_equal(c.income_process()[1]) for c in cals]
     out = {}
     for mode in args.modes.split(","):
         kw = dict(n_a=args.n_a, device=dev, method="brent", resident=mode == "resident", groups=1)
@@ -74,14 +82,20 @@ def main():
             prof = (ctypes.c_double * (8 * len(cals)))()
             n = h.lib.aiy_ge_last_profile(h.h, prof, len(cals))
             p = np.array(prof[:8 * n]).reshape(n, 8)
+            reduced = ctypes.c_int32()
+            h.check(h.lib.aiy_ge_last_iid_cells(h.h, ctypes.byref(reduced)), "iid cells")
+            out["iid_cells"] = [c for c in range(n) if iid[c]]
+            out["reduced_solves"] = int(reduced.value)
+            print(f"[profile] i.i.d. cells {out['iid_cells']}; {reduced.value} ran the asset-grid solve",
+                  file=sys.stderr, flush=True)
             rows = []
             for c in range(n):
                 egm, lot, hist, k, tot, cyc, mv, ev = p[c]
                 rows.append(dict(cell=c, egm_us=round(egm, 1), lottery_us=round(lot, 1), hist_us=round(hist, 1),
                                  k_us=round(k, 1), total_us=round(tot, 1), egm_cycles=int(cyc), matvecs=int(mv),
                                  evaluations=int(ev), us_per_cycle=round(egm / max(1, cyc), 2),
-                                 us_per_matvec=round(hist / max(1, mv), 2)))
-                print(f"[profile] cell {c:2d}: total {tot / 1e3:6.2f} ms  egm {egm / 1e3:6.2f} ms ({int(cyc):5d} cyc, "
+                                 us_per_matvec=round(hist / max(1, mv), 2), iid=bool(iid[c])))
+                print(f"[profile] cell {c:2d}{' iid' if iid[c] else '    '}: total {tot / 1e3:6.2f} ms  egm {egm / 1e3:6.2f} ms ({int(cyc):5d} cyc, "
                       f"{egm / max(1, cyc):5.2f} us)  lottery {lot / 1e3:5.2f} ms  hist {hist / 1e3:6.2f} ms "
                       f"({int(mv):5d} mv, {hist / max(1, mv):5.2f} us)  K {k / 1e3:5.2f} ms  evals {int(ev)}",
                       file=sys.stderr, flush=True)
