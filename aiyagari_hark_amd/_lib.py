@@ -171,6 +171,11 @@ SIGNATURES = {
     "aiy_transition_forward_marginals": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                           ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                           c_double_p, c_double_p, vp, vp]),
+    "aiy_transition_any_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                       ctypes.c_int32]),
+    "aiy_transition_forward_any": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_double_p,
+                                                    c_double_p, vp, c_int32_p, vp]),
     "aiy_jacobian_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "aiy_jacobian_fanout": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp]),

@@ -237,9 +237,11 @@ class AggregateSimulation:
     stats: _stats.WealthStats | None   # [n_cal][n+1] wealth statistics of every period (percentiles=)
     mass: torch.Tensor       # [n_cal][S][n_a] device: the distribution after the last period
     gap: np.ndarray          # [n_cal] max_t |K - K_lin| / K*: the accuracy measure
+    rows_turned: int | None = None   # rows="any": lottery rows with a decreasing pair, all chunks; else None
 
 
-def simulate(batch, model, pol, eps, chunk=64, percentiles=None, mass0=None, want_c=True, timings=None):
+def simulate(batch, model, pol, eps, chunk=64, percentiles=None, mass0=None, want_c=True, timings=None,
+             rows="monotone"):
     """The economy of ``batch`` under the history of TFP innovations ``eps`` ([n] or [n_cal][n]),
     from the distribution ``mass0`` (default: ``batch.mass``, the steady state).  In chunks of at
     most ``chunk`` periods: the chunk's expectations go to the device, aiy_aggregate_lotteries
@@ -250,7 +252,17 @@ def simulate(batch, model, pol, eps, chunk=64, percentiles=None, mass0=None, wan
     milliseconds of the stages (each stage is then synchronised).
 
     A shock so large that a linearised policy is no longer increasing in assets fails the
-    forward sweep's row check: AiyagariLibError (AIY_ERR_UNSUPPORTED)."""
+    forward sweep's row check: AiyagariLibError (AIY_ERR_UNSUPPORTED).  That is the default,
+    ``rows="monotone"``, and it still refuses: on fine grids (from about 1 000 points) a linearised
+    policy swaps a few neighbouring nodes at the policy's kinks and the run stops there.
+    ``rows="any"`` moves the mass with ``transition_forward(rows="any")`` instead,
+    which runs through such rows, and fills ``AggregateSimulation.rows_turned`` with their number
+    over all chunks; it still refuses a row turned so far that its windows hold more than
+    4 (n_a + 1) sources.  Where the default runs, both give the same bits."""
+    if rows not in ("monotone", "any"):
+        raise ValueError(f"rows must be 'monotone' or 'any', got {rows!r}")
+    what = "transition_any" if rows == "any" else "transition"
+    turned = 0 if rows == "any" else None
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     dev = batch.device
     chunk = int(chunk)
@@ -282,7 +294,7 @@ def simulate(batch, model, pol, eps, chunk=64, percentiles=None, mass0=None, wan
     for t0 in range(0, n, chunk):
         L = min(chunk, n - t0)
         if L not in works:
-            works[L] = _lib.work_space(dev, "transition", "transition", n_cal=n_cal, S=S, n_a=n_a, T=L)
+            works[L] = _lib.work_space(dev, what, "transition", n_cal=n_cal, S=S, n_a=n_a, T=L)
         X = torch.as_tensor(np.ascontiguousarray(ex.X[:, t0:t0 + L])).to(dev)
         aggregate_lotteries(batch, pol, X, lo[:L], wlo[:L])
         stage("synthesis")
@@ -293,8 +305,11 @@ def simulate(batch, model, pol, eps, chunk=64, percentiles=None, mass0=None, wan
             R[:, :L] += ex.dr[:, t0:t0 + L]
             w[:, :L] += ex.dw[:, t0:t0 + L]
             R, w = _tr._device(R, dev), _tr._device(w, dev)
-        Ks, Cc = _tr.transition_forward(batch, lo[:L], wlo[:L], mass, L, works[L], R, w, want_c=want_c,
-                                        marg=marg_c[:L + 1] if marg is not None else None)
+        out = _tr.transition_forward(batch, lo[:L], wlo[:L], mass, L, works[L], R, w, want_c=want_c,
+                                     marg=marg_c[:L + 1] if marg is not None else None, rows=rows)
+        Ks, Cc = out[0], out[1]
+        if rows == "any":
+            turned += out[2]
         K[:, t0:t0 + L + 1] = Ks
         if want_c:
             C[:, t0:t0 + L] = Cc
@@ -307,7 +322,7 @@ def simulate(batch, model, pol, eps, chunk=64, percentiles=None, mass0=None, wan
         stage("statistics")
     gap = np.max(np.abs(K - ex.K_lin), axis=1) / model.K
     return AggregateSimulation(K=K, C=C, Z=ex.Z, r=model.r[:, None] + ex.dr, w=model.w[:, None] + ex.dw, K_lin=ex.K_lin,
-                               stats=ws, mass=mass, gap=gap)
+                               stats=ws, mass=mass, gap=gap, rows_turned=turned)
 
 
 def saving_rule(sim, burn=0):

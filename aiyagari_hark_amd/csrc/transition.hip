@@ -31,6 +31,12 @@
 //   tr_marginal_kernel   (aiy_transition_forward_marginals only) the sum over s, ascending, of the
 //                        mass a period's step just wrote: thread = (calibration, node).
 //
+//   tr_windows_kernel    (aiy_transition_forward_any) in place of tr_range_kernel for
+//                        rows that need not be monotone: a workgroup per row, jlo / jhi from the
+//                        row's prefix maximum and suffix minimum, the range and work checks and the
+//                        count of turned rows; tr_forward_kernel<., true> then pulls through the
+//                        windows with lo as the predicate.
+//
 // Offsets into the [T][n_cal][S][n_a] arrays are size_t (24 x 300 x 7 x 10 000 > 2^31).
 #include "common.h"
 #include "egm_common.h"
@@ -327,10 +333,157 @@ int32_t tr_build_ranges(aiy_handle* h, int n_cal, int S, int n_a, int T, const i
   return AIY_OK;
 }
 
+// The windows of rows that need not be monotone (transition_common.h): one
+// workgroup per row r0 + blockIdx.y S + blockIdx.x of the [T n_cal S] rows.  Thread k owns
+// row_chunk's chunk k.  It reduces the chunk's maximum and minimum, the block scans them (an
+// exclusive prefix maximum and an exclusive suffix minimum over the 256 chunks: wave shuffles,
+// then the four wave totals through LDS), and the thread walks its chunk twice: ascending with the
+// running prefix maximum M, writing jlo[d] = j for d in (M, lo[j]] where lo[j] raises it, and
+// descending with the running suffix minimum m, writing jhi[d] = j + 1 for d in [lo[j], m) where
+// lo[j] lowers it -- tr_range_kernel's pattern.  The last thread closes jlo (d above the row's
+// maximum: n_a), thread 0 closes jhi (d below the row's minimum: 0, and jhi[n_a] = n_a).  Every d
+// in [0, n_a] is written exactly once per array.
+// A row with an entry outside [0, n_a - 2] raises flag bit 1 (value 1) and writes nothing: the
+// block leaves before the first write loop.  The row's sum over d of jhi[d] - jlo[d] is formed
+// from the same steps that write (j times the number of d a step writes; integers, thread order):
+// above kTrAnyCap (n_a + 1) it raises flag bit 2 (value 2).  flag[1] counts the rows with at
+// least one decreasing pair.
+// STAGED (rows of at most kTrWinStage entries): the block first copies the row into LDS, one
+// entry per thread and round, and the three walks read it there -- a thread's chunk is contiguous,
+// so the walks' own loads are a chunk apart from lane to lane.
+#ifndef AIY_TR_WIN_STAGE
+#define AIY_TR_WIN_STAGE 12288
+#endif
+constexpr int kTrWinStage = AIY_TR_WIN_STAGE;
+
+template <bool STAGED>
+__global__ __launch_bounds__(kTrBlock) void tr_windows_kernel(int S, int n_a, size_t r0, const int* __restrict__ lo,
+                                                              int* __restrict__ jlo, int* __restrict__ jhi,
+                                                              int* flag) {
+  const size_t r = r0 + (size_t)blockIdx.y * S + blockIdx.x;
+  const int* L = lo + r * n_a;
+  int* Jl = jlo + r * (n_a + 1);
+  int* Jh = jhi + r * (n_a + 1);
+  const int k = threadIdx.x, lane = k & (kWave - 1), wave = k / kWave;
+  __shared__ int s_row[STAGED && kTrWinStage > 0 ? kTrWinStage : 1];
+  if constexpr (STAGED) {
+    for (int j = k; j < n_a; j += kTrBlock) s_row[j] = L[j];
+    __syncthreads();
+    L = s_row;
+  }
+  int j0, j1;
+  row_chunk(n_a, k, j0, j1);
+  // the chunk's extremes, the range check and the decreasing pairs (the pair (j0 - 1, j0) is this thread's)
+  int cmax = -1, cmin = n_a;
+  bool bad = false, turned = false;
+  int prev = j0 > 0 && j0 < j1 ? L[j0 - 1] : -1;
+  for (int j = j0; j < j1; ++j) {
+    const int v = L[j];
+    bad |= v < 0 || v > n_a - 2;
+    turned |= v < prev;
+    cmax = v > cmax ? v : cmax;
+    cmin = v < cmin ? v : cmin;
+    prev = v;
+  }
+  if (__syncthreads_or(bad)) {   // block-uniform: nothing of this row is written
+    if (k == 0) atomicOr(flag, 1);
+    return;
+  }
+  // inclusive scans in the wave, the wave totals through LDS
+  int pmax = cmax, smin = cmin;
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const int u = __shfl_up(pmax, o, kWave), v = __shfl_down(smin, o, kWave);
+    if (lane >= o) pmax = u > pmax ? u : pmax;
+    if (lane + o < kWave) smin = v < smin ? v : smin;
+  }
+  __shared__ int s_max[kTrWaves], s_min[kTrWaves];
+  __shared__ long long s_sum[kTrWaves];
+  if (lane == kWave - 1) s_max[wave] = pmax;
+  if (lane == 0) s_min[wave] = smin;
+  // exclusive: the neighbour lane's inclusive value, then the waves before / after this one
+  int M = __shfl_up(pmax, 1, kWave), m = __shfl_down(smin, 1, kWave);
+  if (lane == 0) M = -1;
+  if (lane == kWave - 1) m = n_a;
+  __syncthreads();
+  for (int q = 0; q < kTrWaves; ++q) {
+    if (q < wave) M = s_max[q] > M ? s_max[q] : M;
+    if (q > wave) m = s_min[q] < m ? s_min[q] : m;
+  }
+  // every entry is in [0, n_a - 2] from here on, so M in [-1, n_a - 2] and m in [0, n_a]
+  long long sum = 0;   // sum of the jhi this thread writes minus sum of the jlo it writes
+  for (int j = j0; j < j1; ++j) {
+    const int v = L[j];
+    if (v > M) {
+      for (int d = M + 1; d <= v; ++d) Jl[d] = j;
+      sum -= (long long)(v - M) * j;
+      M = v;
+    }
+  }
+  if (k == kTrBlock - 1) {   // its inclusive prefix is the row's maximum
+    for (int d = M + 1; d <= n_a; ++d) Jl[d] = n_a;
+    sum -= (long long)(n_a - M) * n_a;
+  }
+  for (int j = j1 - 1; j >= j0; --j) {
+    const int v = L[j];
+    if (v < m) {
+      for (int d = v; d < m; ++d) Jh[d] = j + 1;
+      sum += (long long)(m - v) * (j + 1);
+      m = v;
+    }
+  }
+  if (k == 0) {   // its inclusive suffix is the row's minimum (n_a >= 2: chunk 0 is never empty)
+    for (int d = 0; d < m; ++d) Jh[d] = 0;
+    Jh[n_a] = n_a;
+    sum += n_a;
+  }
+  // the row's window length and whether any pair turned
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, kWave);
+  if (lane == 0) s_sum[wave] = sum;
+  const int any_turned = __syncthreads_or(turned);
+  if (k == 0) {
+    long long tot = 0;
+    for (int q = 0; q < kTrWaves; ++q) tot += s_sum[q];
+    if (tot > (long long)kTrAnyCap * ((long long)n_a + 1)) atomicOr(flag, 2);
+    if (any_turned) atomicAdd(flag + 1, 1);
+  }
+}
+
+int32_t tr_build_windows(aiy_handle* h, int n_cal, int S, int n_a, int T, const int* lo, int* jlo, int* jhi,
+                         int* d_flag, int* rows_turned, hipStream_t st) {
+  AIY_HIP(h, hipMemsetAsync(d_flag, 0, 2 * sizeof(int), st));
+  const long long n_tc = (long long)T * n_cal;   // (period, calibration) pairs, <= 65535 per launch
+  for (long long z0 = 0; z0 < n_tc; z0 += 65535) {
+    const unsigned nz = (unsigned)std::min<long long>(65535, n_tc - z0);
+    if (n_a <= kTrWinStage)
+      hipLaunchKernelGGL(tr_windows_kernel<true>, dim3(S, nz), dim3(kTrBlock), 0, st, S, n_a, (size_t)z0 * S, lo, jlo,
+                         jhi, d_flag);
+    else
+      hipLaunchKernelGGL(tr_windows_kernel<false>, dim3(S, nz), dim3(kTrBlock), 0, st, S, n_a, (size_t)z0 * S, lo, jlo,
+                         jhi, d_flag);
+  }
+  AIY_CHECK_LAUNCH(h);
+  int flag[2] = {0, 0};
+  AIY_HIP(h, hipMemcpyAsync(flag, d_flag, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  AIY_HIP(h, hipStreamSynchronize(st));
+  if (flag[0] & 1)
+    return fail(h, AIY_ERR_UNSUPPORTED, "transition lottery check failed: a row of lo leaves [0, n_a - 2]");
+  if (flag[0] & 2)
+    return fail(h, AIY_ERR_UNSUPPORTED,
+                "transition lottery check failed: a row of lo is too disordered for the windowed pull (its windows "
+                "hold more than %d (n_a + 1) = %lld sources)",
+                kTrAnyCap, (long long)kTrAnyCap * ((long long)n_a + 1));
+  if (rows_turned) *rows_turned = flag[1];
+  return AIY_OK;
+}
+
 struct TrFwd {
   int n_cal, S, n_a, T, nblk;
   const double* wlo;     // [T][n_cal][S][n_a]
-  const int* jb;         // [T][n_cal][S][n_a + 1]
+  const int* jb;         // [T][n_cal][S][n_a + 1]; ANY: jlo
+  const int* jhi;        // ANY: [T][n_cal][S][n_a + 1]
+  const int* lo;         // ANY: [T][n_cal][S][n_a]
   const double* P;       // [n_cal][S][S]
   const double* a_grid;  // [n_cal][n_a]
   const double* R;       // [n_cal][T + 1] (WITH_C)
@@ -367,7 +520,9 @@ __global__ __launch_bounds__(kTrBlock) void tr_K0_kernel(TrFwd A, const double* 
   if (threadIdx.x == 0) A.Kpart[(size_t)cal * A.nblk + blockIdx.x] = k;
 }
 
-template <bool WITH_C>
+// ANY: the windowed pull of rows that need not be monotone (A.jb = jlo, A.jhi, A.lo); everything
+// behind the pull is the same code.
+template <bool WITH_C, bool ANY>
 __global__ __launch_bounds__(kTrBlock) void tr_forward_kernel(TrFwd A, int t, const double* __restrict__ mass,
                                                               double* __restrict__ mass_out) {
   const int S = A.S, n_a = A.n_a;
@@ -388,9 +543,14 @@ __global__ __launch_bounds__(kTrBlock) void tr_forward_kernel(TrFwd A, int t, co
   for (int s = p.wave; s < S; s += kTrWaves) {
     double ls = 0.0;
     if constexpr (WITH_C) ls = wt * A.lab[p.rows + s];
-    Tl[s * kTrCols + p.lane] =
-        tr_pull<WITH_C>(A.jb + (trow + s) * (size_t)(n_a + 1), A.wlo + (trow + s) * (size_t)n_a,
-                        mass + (p.rows + s) * (size_t)n_a, d, p.active, p.lane, ag, Rt, ls, ad, cacc);
+    const size_t jrow = (trow + s) * (size_t)(n_a + 1), lrow = (trow + s) * (size_t)n_a;
+    const double* Q = mass + (p.rows + s) * (size_t)n_a;
+    if constexpr (ANY)
+      Tl[s * kTrCols + p.lane] = tr_pull<WITH_C, true>(A.jb + jrow, A.wlo + lrow, Q, d, p.active, p.lane, ag, Rt, ls, ad,
+                                                       cacc, A.lo + lrow, A.jhi + jrow);
+    else
+      Tl[s * kTrCols + p.lane] =
+          tr_pull<WITH_C>(A.jb + jrow, A.wlo + lrow, Q, d, p.active, p.lane, ag, Rt, ls, ad, cacc);
   }
   __syncthreads();
   // mix: wave w forms mass'[s'] for s' = w, w + 4, ...
@@ -433,10 +593,11 @@ __global__ void tr_sum_kernel(TrFwd A, double* __restrict__ Ks, double* __restri
   }
 }
 
+template <bool ANY>
 static void launch_fwd(const TrFwd& A, int t, bool with_c, const double* src, double* dst, hipStream_t st) {
   const dim3 grid(A.nblk, A.n_cal);
-  if (with_c) hipLaunchKernelGGL((tr_forward_kernel<true>), grid, dim3(kTrBlock), 0, st, A, t, src, dst);
-  else hipLaunchKernelGGL((tr_forward_kernel<false>), grid, dim3(kTrBlock), 0, st, A, t, src, dst);
+  if (with_c) hipLaunchKernelGGL((tr_forward_kernel<true, ANY>), grid, dim3(kTrBlock), 0, st, A, t, src, dst);
+  else hipLaunchKernelGGL((tr_forward_kernel<false, ANY>), grid, dim3(kTrBlock), 0, st, A, t, src, dst);
 }
 
 // g[dist][j] = ((mass[dist][0][j] + mass[dist][1][j]) + ...) + mass[dist][S - 1][j]: the marginal
@@ -476,7 +637,7 @@ static bool tr_sizes_ok(int n_cal, int S, int n_a, int T) {
   return tr_pull_sizes_ok(n_cal, S, n_a) && T >= 1;
 }
 
-static TrWork tr_work(Carve c, int n_cal, int S, int n_a, int T) {
+static TrWork tr_work_take(Carve& c, int n_cal, int S, int n_a, int T) {
   TrWork L;
   L.nblk = tr_nblk(n_a);
   L.tab_doubles = (size_t)n_cal * S * (n_a + 1);
@@ -491,6 +652,23 @@ static TrWork tr_work(Carve c, int n_cal, int S, int n_a, int T) {
   L.bytes = c.bytes();
   return L;
 }
+static TrWork tr_work(Carve c, int n_cal, int S, int n_a, int T) { return tr_work_take(c, n_cal, S, n_a, T); }
+
+// aiy_transition_forward_any: tr_work's regions, then the second window array and the counters
+// (the check's flag word and the number of turned rows).
+struct TrAnyWork {
+  TrWork w;       // w.jb holds jlo
+  int *jhi, *count;
+  size_t bytes;
+};
+static TrAnyWork tr_any_work(Carve c, int n_cal, int S, int n_a, int T) {
+  TrAnyWork L;
+  L.w = tr_work_take(c, n_cal, S, n_a, T);
+  L.jhi = c.take<int>((size_t)T * n_cal * S * (n_a + 1));
+  L.count = c.take<int>(256 / sizeof(int));
+  L.bytes = c.bytes();
+  return L;
+}
 
 }  // namespace aiy
 
@@ -499,6 +677,11 @@ using namespace aiy;
 extern "C" int64_t aiy_transition_work_bytes(int32_t n_cal, int32_t S, int32_t n_a, int32_t T) {
   if (!tr_sizes_ok(n_cal, S, n_a, T)) return -1;
   return (int64_t)tr_work(Carve(), n_cal, S, n_a, T).bytes;
+}
+
+extern "C" int64_t aiy_transition_any_work_bytes(int32_t n_cal, int32_t S, int32_t n_a, int32_t T) {
+  if (!tr_sizes_ok(n_cal, S, n_a, T)) return -1;
+  return (int64_t)tr_any_work(Carve(), n_cal, S, n_a, T).bytes;
 }
 
 extern "C" int32_t aiy_transition_backward(aiy_handle* h, const aiy_transition_model* M, void* work, int32_t* lo,
@@ -549,10 +732,13 @@ extern "C" int32_t aiy_transition_backward(aiy_handle* h, const aiy_transition_m
 
 // The forward sweep of aiy_transition_forward; with `marg` also the marginal of every period's
 // mass, [T + 1][n_cal][n_a], one tr_marginal_kernel launch behind the launch that wrote the mass.
+// ANY: aiy_transition_forward_any's -- `work` is tr_any_work's, the check is tr_build_windows and
+// the number of turned rows goes to rows_turned (host, may be null).
+template <bool ANY>
 static int32_t tr_forward_sweep(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T, const int32_t* lo,
                                 const double* wlo, const double* P, const double* a_grid, const double* R,
                                 const double* w, const double* lab, void* work, double* mass, double* Ks_out,
-                                double* C_out, double* marg, aiy_stream stream) {
+                                double* C_out, double* marg, aiy_stream stream, int32_t* rows_turned = nullptr) {
   if (!h) return AIY_ERR_ARG;
   int32_t rc = tr_check(h, n_cal, S, n_a, true, T);
   if (rc) return rc;
@@ -561,16 +747,29 @@ static int32_t tr_forward_sweep(aiy_handle* h, int32_t n_cal, int32_t S, int32_t
   AIY_HIP(h, hipSetDevice(h->device));
   hipStream_t st = as_stream(stream);
   AIY_USE_STREAM(h, st);
-  const TrWork L = tr_work(Carve(work), n_cal, S, n_a, T);
+  TrWork L;
+  int* jhi = nullptr;
+  if constexpr (ANY) {
+    const TrAnyWork LA = tr_any_work(Carve(work), n_cal, S, n_a, T);
+    L = LA.w;
+    jhi = LA.jhi;
+    // the windows of every period and the row checks, before anything is pushed
+    int turned = 0;
+    rc = tr_build_windows(h, n_cal, S, n_a, T, lo, L.jb, jhi, LA.count, &turned, st);
+    if (rc) return rc;
+    if (rows_turned) *rows_turned = turned;
+  } else {
+    L = tr_work(Carve(work), n_cal, S, n_a, T);
+    // inverse index of every period and the row check, before anything is pushed
+    rc = tr_build_ranges(h, n_cal, S, n_a, T, lo, L.jb, L.flag, st);
+    if (rc) return rc;
+  }
   int* jb = L.jb;
   double *alt = L.alt, *d_Ks = L.ks, *d_C = L.c;
-  int* d_flag = L.flag;
-  // inverse index of every period and the row check, before anything is pushed
-  rc = tr_build_ranges(h, n_cal, S, n_a, T, lo, jb, d_flag, st);
-  if (rc) return rc;
   TrFwd A;
   A.n_cal = n_cal; A.S = S; A.n_a = n_a; A.T = T; A.nblk = L.nblk;
   A.wlo = wlo; A.jb = jb; A.P = P; A.a_grid = a_grid; A.R = R; A.w = w; A.lab = lab;
+  A.jhi = jhi; A.lo = ANY ? lo : nullptr;
   A.Kpart = L.kpart;
   A.Cpart = L.cpart;
   const bool with_c = C_out != nullptr;
@@ -580,7 +779,7 @@ static int32_t tr_forward_sweep(aiy_handle* h, int32_t n_cal, int32_t S, int32_t
   for (int t = 0; t < T; ++t) {   // period t reads mass (t even) / alt (t odd)
     const double* src = (t & 1) ? alt : mass;
     double* dst = (t & 1) ? mass : alt;
-    launch_fwd(A, t, with_c, src, dst, st);
+    launch_fwd<ANY>(A, t, with_c, src, dst, st);
     if (marg) tr_launch_marginal(n_cal, S, n_a, dst, marg + (size_t)(t + 1) * per_marg, st);
   }
   const long long n_sum = (long long)(T + 1) * n_cal;
@@ -599,8 +798,8 @@ extern "C" int32_t aiy_transition_forward(aiy_handle* h, int32_t n_cal, int32_t 
                                           const int32_t* lo, const double* wlo, const double* P, const double* a_grid,
                                           const double* R, const double* w, const double* lab, void* work, double* mass,
                                           double* Ks_out, double* C_out, aiy_stream stream) {
-  return tr_forward_sweep(h, n_cal, S, n_a, T, lo, wlo, P, a_grid, R, w, lab, work, mass, Ks_out, C_out, nullptr,
-                          stream);
+  return tr_forward_sweep<false>(h, n_cal, S, n_a, T, lo, wlo, P, a_grid, R, w, lab, work, mass, Ks_out, C_out,
+                                 nullptr, stream);
 }
 
 extern "C" int32_t aiy_transition_forward_marginals(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
@@ -610,6 +809,16 @@ extern "C" int32_t aiy_transition_forward_marginals(aiy_handle* h, int32_t n_cal
                                                     double* C_out, double* marg_out, aiy_stream stream) {
   if (!h) return AIY_ERR_ARG;
   if (!marg_out) return fail(h, AIY_ERR_ARG, "null marg_out");
-  return tr_forward_sweep(h, n_cal, S, n_a, T, lo, wlo, P, a_grid, R, w, lab, work, mass, Ks_out, C_out, marg_out,
-                          stream);
+  return tr_forward_sweep<false>(h, n_cal, S, n_a, T, lo, wlo, P, a_grid, R, w, lab, work, mass, Ks_out, C_out,
+                                 marg_out, stream);
+}
+
+extern "C" int32_t aiy_transition_forward_any(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
+                                              const int32_t* lo, const double* wlo, const double* P,
+                                              const double* a_grid, const double* R, const double* w,
+                                              const double* lab, void* work, double* mass, double* Ks_out,
+                                              double* C_out, double* marg_out, int32_t* rows_turned_out,
+                                              aiy_stream stream) {
+  return tr_forward_sweep<true>(h, n_cal, S, n_a, T, lo, wlo, P, a_grid, R, w, lab, work, mass, Ks_out, C_out,
+                                marg_out, stream, rows_turned_out);
 }

@@ -51,6 +51,17 @@ int32_t tr_build_ranges(aiy_handle* h, int n_cal, int S, int n_a, int T, const i
 // [n_dist][S][n_a] stack (tr_marginal_kernel, transition.hip).  Asynchronous on `st`.
 void tr_launch_marginal(long long n_dist, int S, int n_a, const double* mass, double* g, hipStream_t st);
 
+// The windows of every row of a [T][n_cal][S][n_a] lottery whose rows need not be monotone
+// (tr_windows_kernel, transition.hip): jlo[row][d] = first j whose prefix maximum
+// of lo is >= d, jhi[row][d] = first j whose suffix minimum is > d, d in [0, n_a], so the sources
+// with lo = d lie in [jlo[d], jhi[d]); on a monotone row jlo[d] = jb[d] and jhi[d] = jb[d + 1].
+// Blocks on `st` for d_flag[0] and d_flag[1], the number of rows with a decreasing pair (to
+// *rows_turned).  AIY_ERR_UNSUPPORTED, naming the check, when an entry leaves [0, n_a - 2] or a
+// row's windows hold more than kTrAnyCap (n_a + 1) sources; the arrays are then not to be used.
+constexpr int kTrAnyCap = 4;
+int32_t tr_build_windows(aiy_handle* h, int n_cal, int S, int n_a, int T, const int* lo, int* jlo, int* jhi,
+                         int* d_flag, int* rows_turned, hipStream_t st);
+
 // ---------------------------------------------------------------------------------
 // The 64-column kernels: grid (tr_nblk(n_a), n_cal[, periods]), kTrBlock threads, a kTrTile LDS tile
 // ---------------------------------------------------------------------------------
@@ -76,24 +87,44 @@ __device__ __forceinline__ TrPlace tr_place(int S, int n_a) {
 // than a wave has it summed by the whole wave (lane-strided partials, then wave_sum_lane63).
 // WITH_C: every term times its consumption (Rt ag[j] + ls) - ad is added to cacc.  Every lane of
 // the wave must call it.
-template <bool WITH_C>
+// ANY (rows that need not be monotone, tr_build_windows): J and H are the state's rows of jlo and
+// jhi, L its row of lo.  The sources with lo = d lie in the window [J[d], H[d]) and those with
+// lo = d - 1 in [J[d - 1], H[d - 1]); both are walked as above and a source counts only where L
+// says so, the consumption term included.  On a monotone row the windows are the ranges and
+// every source in them matches: the same terms in the same order.
+template <bool WITH_C, bool ANY = false>
 __device__ __forceinline__ double tr_pull(const int* J, const double* W, const double* Q, int d, bool active, int lane,
-                                          const double* ag, double Rt, double ls, double ad, double& cacc) {
-  int a0 = 0, a1 = 0, a2 = 0;   // lo = d - 1: [a0, a1), lo = d: [a1, a2)
+                                          const double* ag, double Rt, double ls, double ad, double& cacc,
+                                          const int* L = nullptr, const int* H = nullptr) {
+  int a0 = 0, a1 = 0, a2 = 0;   // lo = d - 1: [a0, e1), lo = d: [a1, a2); e1 = a1 unless ANY
+  int h0 = 0;
   if (active) {
     a1 = J[d];
-    a2 = J[d + 1];
-    a0 = d > 0 ? J[d - 1] : a1;
+    if constexpr (ANY) {
+      a2 = H[d];
+      a0 = d > 0 ? J[d - 1] : a1;
+      h0 = d > 0 ? H[d - 1] : a1;
+    } else {
+      a2 = J[d + 1];
+      a0 = d > 0 ? J[d - 1] : a1;
+    }
   }
-  const bool heavy = (a2 - a1 > kWave) || (a1 - a0 > kWave);
+  const int e1 = ANY ? h0 : a1;
+  const bool heavy = (a2 - a1 > kWave) || (e1 - a0 > kWave);
   double ts = 0.0;
   if (!heavy) {
     for (int j = a1; j < a2; ++j) {                      // np.add.at(T, lo, w q), ascending j
+      if constexpr (ANY) {
+        if (L[j] != d) continue;
+      }
       const double term = W[j] * Q[j];
       ts += term;
       if constexpr (WITH_C) cacc += term * ((Rt * ag[j] + ls) - ad);
     }
-    for (int j = a0; j < a1; ++j) {                      // np.add.at(T, lo + 1, (1 - w) q)
+    for (int j = a0; j < e1; ++j) {                      // np.add.at(T, lo + 1, (1 - w) q)
+      if constexpr (ANY) {
+        if (L[j] != d - 1) continue;
+      }
       const double term = (1.0 - W[j]) * Q[j];
       ts += term;
       if constexpr (WITH_C) cacc += term * ((Rt * ag[j] + ls) - ad);
@@ -105,15 +136,26 @@ __device__ __forceinline__ double tr_pull(const int* J, const double* W, const d
     hm &= hm - 1ull;
     const int b0 = __builtin_amdgcn_readlane(a0, hl), b1 = __builtin_amdgcn_readlane(a1, hl),
               b2 = __builtin_amdgcn_readlane(a2, hl);
+    int g1 = b1, dh = 0;   // the end of the lo = d - 1 part; ANY: the heavy lane's column
+    if constexpr (ANY) {
+      g1 = __builtin_amdgcn_readlane(h0, hl);
+      dh = __builtin_amdgcn_readlane(d, hl);
+    }
     double adh = 0.0;
     if constexpr (WITH_C) adh = __shfl(ad, hl, kWave);
     double pa = 0.0, pb = 0.0, pc = 0.0;
     for (int j = b1 + lane; j < b2; j += kWave) {
+      if constexpr (ANY) {
+        if (L[j] != dh) continue;
+      }
       const double term = W[j] * Q[j];
       pa += term;
       if constexpr (WITH_C) pc += term * ((Rt * ag[j] + ls) - adh);
     }
-    for (int j = b0 + lane; j < b1; j += kWave) {
+    for (int j = b0 + lane; j < g1; j += kWave) {
+      if constexpr (ANY) {
+        if (L[j] != dh - 1) continue;
+      }
       const double term = (1.0 - W[j]) * Q[j];
       pb += term;
       if constexpr (WITH_C) pc += term * ((Rt * ag[j] + ls) - adh);

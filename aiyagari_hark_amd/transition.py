@@ -144,13 +144,24 @@ def transition_backward(batch, R, w, m_term, c_term, buffers, export_policy=True
             "aiy_transition_backward")
 
 
-def transition_forward(batch, lo, wlo, mass, T, work, R=None, w=None, want_c=True, stream=None, marg=None):
+def transition_forward(batch, lo, wlo, mass, T, work, R=None, w=None, want_c=True, stream=None, marg=None,
+                       rows="monotone"):
     """aiy_transition_forward on device lotteries [T][n_cal][S][n_a]: advances ``mass`` in
     place from period 0 to period T and returns (Ks [n_cal][T+1], C [n_cal][T] or None).
     With ``marg`` (device [T+1][n_cal][n_a]) the sweep is aiy_transition_forward_marginals: the
     same results, and marg[t] = the sum over states of mass_t, t = 0 .. T.
     Raises AiyagariLibError (AIY_ERR_UNSUPPORTED) when a lottery row fails the monotone /
-    range check; mass (and marg) is then untouched."""
+    range check; mass (and marg) is then untouched.
+
+    ``rows="monotone"`` (the default) still refuses a lottery with a row that is not
+    non-decreasing.  ``rows="any"`` is aiy_transition_forward_any: such rows run
+    through the windowed pull, ``work`` must come from ``_lib.work_space(dev, "transition_any",
+    ...)``, and the call returns ``(Ks, C, rows_turned)``, the number of rows with a decreasing
+    pair.  It refuses (AIY_ERR_UNSUPPORTED, everything untouched) an entry outside [0, n_a - 2]
+    and a row so disordered that its windows hold more than 4 (n_a + 1) sources; on monotone
+    lotteries it gives the bits of the default.  Any other value: ValueError."""
+    if rows not in ("monotone", "any"):
+        raise ValueError(f"rows must be 'monotone' or 'any', got {rows!r}")
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     h = _lib.handle(batch.device.index)
     Ks = np.zeros((n_cal, T + 1))
@@ -159,11 +170,20 @@ def transition_forward(batch, lo, wlo, mass, T, work, R=None, w=None, want_c=Tru
             _lib.ptr(R) if want_c else None, _lib.ptr(w) if want_c else None,
             _lib.ptr(batch.d_lab) if want_c else None, _lib.ptr(work), _lib.ptr(mass),
             Ks.ctypes.data_as(_lib.c_double_p), C.ctypes.data_as(_lib.c_double_p) if want_c else None)
+    if marg is not None and (tuple(marg.shape) != (T + 1, n_cal, n_a) or marg.dtype != F64):
+        raise ValueError(f"marg must be float64 [T+1][n_cal][n_a] = {(T + 1, n_cal, n_a)}, got {tuple(marg.shape)}")
+    if rows == "any":
+        need = int(h.lib.aiy_transition_any_work_bytes(n_cal, S, n_a, int(T)))
+        if work.numel() * work.element_size() < need:
+            raise ValueError(f"rows='any' needs a 'transition_any' work space of {need} bytes, got "
+                             f"{work.numel() * work.element_size()}")
+        turned = ctypes.c_int32(0)
+        h.check(h.lib.aiy_transition_forward_any(*args, _lib.ptr(marg), ctypes.byref(turned), _lib.stream_ptr(stream)),
+                "aiy_transition_forward_any")
+        return Ks, C, int(turned.value)
     if marg is None:
         h.check(h.lib.aiy_transition_forward(*args, _lib.stream_ptr(stream)), "aiy_transition_forward")
     else:
-        if tuple(marg.shape) != (T + 1, n_cal, n_a) or marg.dtype != F64:
-            raise ValueError(f"marg must be float64 [T+1][n_cal][n_a] = {(T + 1, n_cal, n_a)}, got {tuple(marg.shape)}")
         h.check(h.lib.aiy_transition_forward_marginals(*args, _lib.ptr(marg), _lib.stream_ptr(stream)),
                 "aiy_transition_forward_marginals")
     return Ks, C

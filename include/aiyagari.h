@@ -598,6 +598,30 @@ int32_t aiy_transition_forward_marginals(aiy_handle* h, int32_t n_cal, int32_t S
                                          void* work, double* mass, double* Ks_out, double* C_out, double* marg_out,
                                          aiy_stream stream);
 
+/* Device scratch of aiy_transition_forward_any: the regions of aiy_transition_work_bytes, then the
+ * second window array ([T][n_cal][S][n_a + 1] int32) and the check's counters; -1 for the same
+ * bad sizes.  A work space of this size also serves aiy_transition_backward.  Host-only. */
+int64_t aiy_transition_any_work_bytes(int32_t n_cal, int32_t S, int32_t n_a, int32_t T);
+
+/* aiy_transition_forward[_marginals] for lotteries whose rows need not be non-decreasing
+ * (DESIGN.md §4r).  Per row, with the prefix maximum and the suffix minimum of lo, the sources
+ * with lo = d lie in a window [jlo[d], jhi[d]); the pull of column d walks the windows of d and
+ * d - 1 in ascending j and adds a source where lo says so -- the order of the push form's two
+ * scattered adds, no atomics, deterministic.  On a lottery whose rows are all non-decreasing
+ * mass, Ks_out, C_out and marg_out have the bits aiy_transition_forward_marginals gives.
+ *   marg_out        DEVICE [T+1][n_cal][n_a] or NULL
+ *   rows_turned_out HOST, one int32, or NULL: the rows (of the T n_cal S) with a decreasing pair
+ *   work            DEVICE, aiy_transition_any_work_bytes(n_cal, S, n_a, T)
+ * Returns AIY_ERR_UNSUPPORTED, with nothing pushed and mass, Ks_out, C_out and marg_out
+ * untouched, if an entry of lo leaves [0, n_a - 2] or if a row is too disordered: its windows
+ * together hold more than 4 (n_a + 1) sources (a sorted row: n_a).  aiy_last_error names which.
+ * The argument checks are aiy_transition_forward's and run before any launch.  BLOCKING. */
+int32_t aiy_transition_forward_any(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
+                                   const int32_t* lo, const double* wlo, const double* P, const double* a_grid,
+                                   const double* R, const double* w, const double* lab, void* work, double* mass,
+                                   double* Ks_out, double* C_out, double* marg_out, int32_t* rows_turned_out,
+                                   aiy_stream stream);
+
 /* ------- sequence-space Jacobian of the household block (build-defined) ------- */
 
 /* The device stages of the fake-news algorithm at a steady state; the backward sweeps are

@@ -4,7 +4,7 @@ at the Table II size: 24 calibrations, n_a = 10 000, T = 300, 1 000 simulated pe
 chunks of 64.
 
   python tools/aggregate_time.py [--n-a N --T T --periods N --chunk C --reps R --sigmas LIST --launch-only
-                                  --out FILE]
+                                  --rows {monotone,any} --out FILE]
       (a) ms of policy_jacobian (three backward sweeps, the lottery means, the differences),
           median of R builds after a warm one;
       (b) ms of one simulation by stage (synthesis launches, forward sweeps, statistics), each
@@ -16,6 +16,13 @@ chunks of 64.
       (c) one synthesis launch by HIP events for several numbers of periods per launch, and in
           the same run aiy_jacobian_contract at the same shape (on the same operands: only the
           time matters) and its TFLOP/s, for comparison.
+--rows any: the simulation of (b) moves the mass with the forward sweep that takes rows which are
+not monotone (DESIGN.md §4r), so the first sigma runs unless a row passes that sweep's work cap;
+the document then also holds rows_turned and
+      (d) the forward sweep of T periods of the steady lottery (monotone, so both forms run it)
+          by the default form and by rows="any", alternating, HIP events, with the same bits
+          checked; and each form's index pass alone (the host clock around a call whose lottery
+          has one entry out of range: it builds the index, reads the flag and returns).
 --launch-only: (c)'s synthesis launches alone (a library built with another period tile is
 measured through AIYAGARI_LIB).  One JSON document, written to --out (default
 profiles/aggregate_time.json)."""
@@ -57,6 +64,72 @@ def synthesis_launches(args, batch, pol, timed, flop_period):
     return launch
 
 
+def forward_forms(args, batch, pol, model, timed):
+    """(d): the forward sweep over T periods of the steady lottery by both forms, and their index
+    passes alone."""
+    import numpy as np
+    import torch
+
+    from aiyagari_hark_amd import _lib
+    from aiyagari_hark_amd._lib import AiyagariLibError
+    from aiyagari_hark_amd.aggregate import aggregate_lotteries
+    from aiyagari_hark_amd.transition import transition_forward
+    n_cal, S, n_a, T, dev = len(batch.cals), batch.S, batch.n_a, args.T, batch.device
+    med = statistics.median
+    lo = torch.empty((T, n_cal, S, n_a), dtype=torch.int32, device=dev)
+    wlo = torch.empty((T, n_cal, S, n_a), dtype=torch.float64, device=dev)
+    for t0 in range(0, T, args.chunk):   # zero expected deviations: the steady lottery in every period
+        L = min(args.chunk, T - t0)
+        X = torch.zeros((n_cal, L, 2 * (pol.dA_R.shape[0])), dtype=torch.float64, device=dev)
+        aggregate_lotteries(batch, pol, X, lo[t0:t0 + L], wlo[t0:t0 + L])
+    R = torch.as_tensor(np.repeat((1.0 + model.r)[:, None], T + 1, axis=1)).to(dev)
+    w = torch.as_tensor(np.repeat(model.w[:, None], T + 1, axis=1)).to(dev)
+    works = {rows: _lib.work_space(dev, what, what, n_cal=n_cal, S=S, n_a=n_a, T=T)
+             for rows, what in (("monotone", "transition"), ("any", "transition_any"))}
+    mass = torch.empty_like(batch.mass)
+    results = {}
+
+    def sweep(rows):
+        mass.copy_(batch.mass)
+        results[rows] = transition_forward(batch, lo, wlo, mass, T, works[rows], R, w, want_c=True, rows=rows)
+
+    ends = {}
+    for rows in works:   # warm, and the bits
+        sweep(rows)
+        ends[rows] = mass.clone()
+    same = bool(torch.equal(ends["monotone"], ends["any"]) and np.array_equal(results["monotone"][0], results["any"][0])
+                and np.array_equal(results["monotone"][1], results["any"][1]))
+    ms = {rows: [] for rows in works}
+    for _ in range(args.reps):
+        for rows in works:
+            ms[rows].append(timed(lambda: sweep(rows)))
+    # the index pass alone: one entry out of range, so the call stops behind its check
+    keep = lo[0, 0, 0, 0].clone()
+    lo[0, 0, 0, 0] = n_a - 1
+    index_ms = {rows: [] for rows in works}
+    for _ in range(args.reps + 1):
+        for rows in works:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            try:
+                sweep(rows)
+                raise SystemExit("an out-of-range lottery was not refused")
+            except AiyagariLibError:
+                pass
+            index_ms[rows].append((time.perf_counter() - t0) * 1e3)
+    lo[0, 0, 0, 0] = keep
+    index_ms = {rows: v[1:] for rows, v in index_ms.items()}
+    m, a = med(ms["monotone"]), med(ms["any"])
+    return dict(periods=T, rows_turned=results["any"][2], same_bits=same, monotone_ms=m, any_ms=a,
+                monotone_all_ms=ms["monotone"], any_all_ms=ms["any"], any_over_monotone=a / m,
+                monotone_ms_per_period=m / T, any_ms_per_period=a / T,
+                index_monotone_ms=med(index_ms["monotone"]), index_any_ms=med(index_ms["any"]),
+                index_monotone_all_ms=index_ms["monotone"], index_any_all_ms=index_ms["any"],
+                index_any_over_monotone=med(index_ms["any"]) / med(index_ms["monotone"]),
+                work_GB={rows: wk.numel() / 1e9 for rows, wk in works.items()},
+                note="the index pass times hold the mass copy, the flag's read-back and the host's return")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-a", type=int, default=10000)
@@ -66,6 +139,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sigmas", default="0.007,0.002,0.0007,0.0002,0")
     ap.add_argument("--launch-only", action="store_true")
+    ap.add_argument("--rows", choices=("monotone", "any"), default="monotone")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "aggregate_time.json"))
     args = ap.parse_args()
 
@@ -126,20 +200,21 @@ def main():
     attempts = []
     for sigma in (float(x) for x in args.sigmas.split(",")):
         try:
-            simulate(batch, model, pol, sigma * draw, chunk=args.chunk, percentiles=[0.5, 0.9])   # also the warm run
+            simulate(batch, model, pol, sigma * draw, chunk=args.chunk, percentiles=[0.5, 0.9],
+                     rows=args.rows)   # also the warm run
             attempts.append(dict(sigma=sigma, ok=True))
             break
         except AiyagariLibError as e:
             attempts.append(dict(sigma=sigma, ok=False, error=str(e)))
     else:
-        raise SystemExit(f"no sigma of {args.sigmas} gives monotone lottery rows")
+        raise SystemExit(f"no sigma of {args.sigmas} gives lottery rows that rows={args.rows!r} takes")
     eps = sigma * draw
     runs, wall = [], []
     for _ in range(args.reps):
         tm = {}
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        sim = simulate(batch, model, pol, eps, chunk=args.chunk, percentiles=[0.5, 0.9], timings=tm)
+        sim = simulate(batch, model, pol, eps, chunk=args.chunk, percentiles=[0.5, 0.9], timings=tm, rows=args.rows)
         wall.append((time.perf_counter() - t0) * 1e3)
         runs.append(tm)
     stage_ms = {k: med([q[k] for q in runs]) for k in runs[0]}
@@ -154,7 +229,9 @@ def main():
     con_TF = con_flop / (med(t_con) * 1e-3) / 1e12
 
     syn_TF = flop_period * n / (stage_ms["synthesis"] * 1e-3) / 1e12
+    forward_ab = forward_forms(args, batch, pol, model, timed) if args.rows == "any" else None
     out = dict(shape=dict(n_cal=n_cal, S=S, n_a=n_a, T=T, periods=n, chunk=args.chunk), reps=args.reps,
+               rows=args.rows, rows_turned=sim.rows_turned, forward_forms=forward_ab,
                sigma=sigma, sigma_attempts=attempts, source_digest=build.source_digest(), library=_lib.LIB_PATH.replace(ROOT + os.sep, ""),
                policy_jacobian_ms=med(t_pol), policy_jacobian_all_ms=t_pol,
                simulate_wall_ms=med(wall), simulate_wall_all_ms=wall, stage_ms=stage_ms, stage_all_ms=runs,
@@ -168,7 +245,7 @@ def main():
                                saving_rule_R2=None if rule is None else rule[:, 3].tolist(),
                                gini_min=sim.stats.gini.min(axis=1).tolist(), gini_max=sim.stats.gini.max(axis=1).tolist()))
     write(args.out, out)
-    print(json.dumps({k: out[k] for k in ("shape", "sigma", "sigma_attempts", "policy_jacobian_ms", "simulate_wall_ms", "stage_ms", "synthesis_TFLOPs",
+    print(json.dumps({k: out[k] for k in ("shape", "rows", "rows_turned", "forward_forms", "simulation", "sigma", "sigma_attempts", "policy_jacobian_ms", "simulate_wall_ms", "stage_ms", "synthesis_TFLOPs",
                                           "synthesis_launch", "contraction_ms", "contraction_TFLOPs",
                                           "synthesis_over_contraction")}, indent=1))
 
