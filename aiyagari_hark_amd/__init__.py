@@ -16,7 +16,9 @@ of the household block (``household_jacobian``, ``impulse_response``) in
 :mod:`aiyagari_hark_amd.aggregate`; wealth statistics of the panel and of histogram
 distributions and paths (``histogram_stats``, ``batch_wealth_stats``, ``path_wealth_stats``) in
 :mod:`aiyagari_hark_amd.stats`; values on the histogram and consumption-equivalent welfare gains
-(``stationary_value``, ``path_value``, ``welfare.welfare``) in :mod:`aiyagari_hark_amd.welfare`.
+(``stationary_value``, ``path_value``, ``welfare.welfare``) in :mod:`aiyagari_hark_amd.welfare`;
+cohorts followed through the lotteries and mobility tables (``mobility``, ``cohort_forward``,
+``wealth_classes``) in :mod:`aiyagari_hark_amd.mobility`.
 """
 from __future__ import annotations
 
@@ -45,4 +47,10 @@ def __getattr__(name):
         import importlib
         welfare = importlib.import_module(__name__ + ".welfare")
         return welfare if name == "welfare" else getattr(welfare, name)
+    if name in ("mobility", "wealth_classes", "cohorts_by_class", "cohorts_by_state", "cohort_forward",
+                "CohortPaths", "MobilityResult"):
+        # ``mobility`` is the module (the import binds the name): its function is ``mobility.mobility``
+        import importlib
+        mobility = importlib.import_module(__name__ + ".mobility")
+        return mobility if name == "mobility" else getattr(mobility, name)
     raise AttributeError(name)

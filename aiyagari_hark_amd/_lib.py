@@ -25,6 +25,8 @@ AIY_OK = 0
 ERRORS = {-1: "AIY_ERR_ARG", -2: "AIY_ERR_HIP", -3: "AIY_ERR_STATE", -4: "AIY_ERR_UNSUPPORTED",
           -5: "AIY_ERR_COMM"}
 AIY_MAX_STATES = 64
+AIY_MAX_COHORTS = 16
+AIY_MAX_CLASSES = 32
 AIY_SOW_DOUBLES = 8
 AIY_OPT_USE_GRAPHS = 1
 AIY_OPT_RESIDENT = 2
@@ -176,6 +178,11 @@ SIGNATURES = {
     "aiy_transition_forward_any": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                     ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_double_p,
                                                     c_double_p, vp, c_int32_p, vp]),
+    "aiy_cohort_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int32]),
+    "aiy_cohort_forward": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp,
+                                            c_int32_p, vp, vp, c_double_p, c_double_p, c_double_p, c_double_p, vp]),
     "aiy_jacobian_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "aiy_jacobian_fanout": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp]),

@@ -69,6 +69,7 @@ struct aiy_handle {
   std::vector<double> ge_evlog;      // [n_cal][32][6] per-evaluation log of the last search
   aiy::DeviceBuffer stats;           // wealth statistics (stats.hip): sort / scan scratch
   aiy::DeviceBuffer welf;            // welfare (welfare.hip): the [n_cal][S] sums of aiy_value_reduce
+  aiy::DeviceBuffer cohort;          // cohorts (cohort.hip): K, C, occ and inc of every period (CoSums)
   // resident panel: tagged partial-sum granules + timeout word; option
   aiy::DeviceBuffer res_sync;
   bool use_resident = true;

@@ -493,18 +493,6 @@ struct TrFwd {
   double* Cpart;         // [T][n_cal][nblk]
 };
 
-// Block sum in a fixed order (xor butterflies per wave, waves ascending); thread 0 holds it.
-__device__ __forceinline__ double tr_block_sum(double v, double* red) {
-  v = wave_sum_fixed(v);
-  __syncthreads();
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-  __syncthreads();
-  double k = 0.0;
-  if (threadIdx.x == 0)
-    for (int q = 0; q < kTrWaves; ++q) k += red[q];
-  return k;
-}
-
 // Ks[0] = sum mass_0 a with the column partition of the forward step.
 __global__ __launch_bounds__(kTrBlock) void tr_K0_kernel(TrFwd A, const double* __restrict__ mass) {
   const int cal = blockIdx.y, S = A.S, n_a = A.n_a;

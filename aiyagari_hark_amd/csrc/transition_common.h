@@ -172,6 +172,110 @@ __device__ __forceinline__ double tr_pull(const int* J, const double* W, const d
   return ts;
 }
 
+// tr_pull (monotone rows) for GC masses at once: Q is the state's row of the first mass and mass
+// g's row lies g * gstride doubles behind it (g < ng <= GC live; the others repeat the last live
+// one and their results are the caller's to drop).  The ranges, their order, the whole-wave path
+// and, mass by mass, every floating-point operation are tr_pull's -- W[j] and the consumption
+// factor are loaded / formed once per source and the GC sums ts[g] (and cacc[g], WITH_C) are kept
+// in registers -- so ts[g] and cacc[g] have the bits tr_pull gives on mass g alone.  Every lane
+// of the wave must call it.
+template <int GC, bool WITH_C>
+__device__ __forceinline__ void tr_pull_multi(const int* J, const double* W, const double* Q, size_t gstride, int ng,
+                                              int d, bool active, int lane, const double* ag, double Rt, double ls,
+                                              double ad, double (&ts)[GC], double (&cacc)[GC]) {
+  int a0 = 0, a1 = 0, a2 = 0;   // lo = d - 1: [a0, a1), lo = d: [a1, a2)
+  if (active) {
+    a1 = J[d];
+    a2 = J[d + 1];
+    a0 = d > 0 ? J[d - 1] : a1;
+  }
+  const bool heavy = (a2 - a1 > kWave) || (a1 - a0 > kWave);
+  auto row = [&](int g) { return Q + (size_t)(g < ng ? g : ng - 1) * gstride; };   // wave-uniform
+#pragma unroll
+  for (int g = 0; g < GC; ++g) ts[g] = 0.0;
+  if (!heavy) {
+    for (int j = a1; j < a2; ++j) {                      // np.add.at(T, lo, w q), ascending j
+      const double wj = W[j];
+      double cf = 0.0;
+      if constexpr (WITH_C) cf = (Rt * ag[j] + ls) - ad;
+#pragma unroll
+      for (int g = 0; g < GC; ++g) {
+        const double term = wj * row(g)[j];
+        ts[g] += term;
+        if constexpr (WITH_C) cacc[g] += term * cf;
+      }
+    }
+    for (int j = a0; j < a1; ++j) {                      // np.add.at(T, lo + 1, (1 - w) q)
+      const double wj = 1.0 - W[j];
+      double cf = 0.0;
+      if constexpr (WITH_C) cf = (Rt * ag[j] + ls) - ad;
+#pragma unroll
+      for (int g = 0; g < GC; ++g) {
+        const double term = wj * row(g)[j];
+        ts[g] += term;
+        if constexpr (WITH_C) cacc[g] += term * cf;
+      }
+    }
+  }
+  unsigned long long hm = __ballot(heavy);
+  while (hm) {   // wave-uniform: the whole wave sums one lane's ranges
+    const int hl = __builtin_ctzll(hm);
+    hm &= hm - 1ull;
+    const int b0 = __builtin_amdgcn_readlane(a0, hl), b1 = __builtin_amdgcn_readlane(a1, hl),
+              b2 = __builtin_amdgcn_readlane(a2, hl);
+    double adh = 0.0;
+    if constexpr (WITH_C) adh = __shfl(ad, hl, kWave);
+    double pa[GC], pb[GC], pc[GC];
+#pragma unroll
+    for (int g = 0; g < GC; ++g) pa[g] = pb[g] = pc[g] = 0.0;
+    for (int j = b1 + lane; j < b2; j += kWave) {
+      const double wj = W[j];
+      double cf = 0.0;
+      if constexpr (WITH_C) cf = (Rt * ag[j] + ls) - adh;
+#pragma unroll
+      for (int g = 0; g < GC; ++g) {
+        const double term = wj * row(g)[j];
+        pa[g] += term;
+        if constexpr (WITH_C) pc[g] += term * cf;
+      }
+    }
+    for (int j = b0 + lane; j < b1; j += kWave) {
+      const double wj = 1.0 - W[j];
+      double cf = 0.0;
+      if constexpr (WITH_C) cf = (Rt * ag[j] + ls) - adh;
+#pragma unroll
+      for (int g = 0; g < GC; ++g) {
+        const double term = wj * row(g)[j];
+        pb[g] += term;
+        if constexpr (WITH_C) pc[g] += term * cf;
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < GC; ++g) {
+      const double ta = wave_sum_lane63(pa[g]), tb = wave_sum_lane63(pb[g]);
+      const double tot = __shfl(ta, kWave - 1, kWave) + __shfl(tb, kWave - 1, kWave);
+      double tc = 0.0;
+      if constexpr (WITH_C) tc = __shfl(wave_sum_lane63(pc[g]), kWave - 1, kWave);
+      if (lane == hl) {
+        ts[g] = tot;
+        if constexpr (WITH_C) cacc[g] += tc;
+      }
+    }
+  }
+}
+
+// Block sum in a fixed order (xor butterflies per wave, waves ascending); thread 0 holds it.
+__device__ __forceinline__ double tr_block_sum(double v, double* red) {
+  v = wave_sum_fixed(v);
+  __syncthreads();
+  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
+  __syncthreads();
+  double k = 0.0;
+  if (threadIdx.x == 0)
+    for (int q = 0; q < kTrWaves; ++q) k += red[q];
+  return k;
+}
+
 // The two mixes of the lane's column of the LDS tile X[s][lane] by P [S][S] (wave-uniform):
 // forward, mass'[sp] = sum over s, ascending, of P[s, sp] X[s] (hist_mix_kernel's order) ...
 __device__ __forceinline__ double tr_mix_forward(const double* P, const double* X, int S, int sp, int lane) {

@@ -247,10 +247,11 @@ class TransitionResult:
     status: np.ndarray       # [n_cal] 0: converged; bit 1: stopped at max_iter
     stats: _stats.WealthStats | None = None   # [n_cal][T+1] wealth statistics of the path (percentiles=)
     welfare: object | None = None             # welfare.WelfareResult of the path against the steady state (welfare=True)
+    cohorts: object | None = None             # mobility.CohortPaths of the wealth classes of mass0 (cohorts=)
 
 
 def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=None, m_term=None, c_term=None,
-                     method="damped", jacobian=None, percentiles=None, welfare=False):
+                     method="damped", jacobian=None, percentiles=None, welfare=False, cohorts=None):
     """Equilibrium capital path of every calibration of ``batch`` after the TFP path Z
     ([T+1] or [n_cal][T+1], Z[T] = 1), from the distribution mass0 (default: batch.mass, the
     steady state) to the terminal policy (default: batch.last_tables).
@@ -275,13 +276,22 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
     through the solved path from mass0 against staying at the steady state of ``batch``
     (DESIGN.md §4m): V_base = ``welfare.stationary_value(batch)``, V = ``welfare.path_value`` on
     the lotteries and prices of the last evaluation with V_base as the value from period T on.
-    Nothing else of the result changes."""
+    Nothing else of the result changes.
+
+    ``cohorts`` (a tuple of percentiles in (0, 1), strictly ascending): also
+    ``TransitionResult.cohorts``, the ``mobility.CohortPaths`` of the wealth classes of mass0
+    between these percentiles (``mobility.wealth_classes``), swept from mass0 on the lotteries and
+    prices of the last evaluation: every class's capital and consumption path
+    and its mass by wealth class and income state.  Nothing else of the result changes."""
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     T = int(T)
     if method not in ("damped", "newton"):
         raise ValueError(f"method must be 'damped' or 'newton', got {method!r}")
     if method == "damped" and jacobian is not None:
         raise ValueError("jacobian= is only used by method='newton'")
+    if cohorts is not None:
+        from . import mobility as _mobility
+        cohorts = _mobility._check_class_percentiles(cohorts)
     Z = np.broadcast_to(np.asarray(Z, dtype=np.float64), (n_cal, T + 1))
     if m_term is None or c_term is None:
         if getattr(batch, "last_tables", None) is None:
@@ -340,8 +350,13 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
         V_base = _welfare.stationary_value(batch)
         V = _welfare.path_value(batch, buffers.lo, buffers.wlo, 1.0 + r, w, V_base)
         gains = _welfare.welfare(batch, V, V_base, mass0)
+    followed = None
+    if cohorts is not None:
+        edges = _mobility.wealth_classes(batch, cohorts, mass=mass0)
+        followed = _mobility.cohort_forward(batch, buffers.lo, buffers.wlo,
+                                            _mobility.cohorts_by_class(batch, edges, mass=mass0), T, edges, R=1.0 + r, w=w)
     return TransitionResult(K=K, r=r, w=w, C=C, iterations=iterations, residual=residual, status=status,
-                            stats=path_stats, welfare=gains)
+                            stats=path_stats, welfare=gains, cohorts=followed)
 
 
 def steady_rate(batch):

@@ -622,6 +622,45 @@ int32_t aiy_transition_forward_any(aiy_handle* h, int32_t n_cal, int32_t S, int3
                                    double* Ks_out, double* C_out, double* marg_out, int32_t* rows_turned_out,
                                    aiy_stream stream);
 
+/* ---------- cohorts on the forward sweep: mobility (build-defined) ---------- */
+
+#define AIY_MAX_COHORTS 16   /* G: masses one aiy_cohort_forward call carries */
+#define AIY_MAX_CLASSES 32   /* Q: wealth classes of the occupancy            */
+
+/* Device scratch of aiy_cohort_forward (caller-owned `work`): the inverse index of the n_lot
+ * lottery periods, the ping-pong partner of the G cohorts, the blocks' partial sums of
+ * min(n_lot, 7) + 1 periods and the class edges; -1 for bad sizes (n_lot < 1, G outside
+ * 1..AIY_MAX_COHORTS, Q outside 1..AIY_MAX_CLASSES, S and n_a as aiy_transition_work_bytes).
+ * A multiple of 256.  Host-only. */
+int64_t aiy_cohort_work_bytes(int32_t n_cal, int32_t S, int32_t n_a, int32_t n_lot, int32_t G, int32_t Q);
+
+/* Forward sweep of G cohorts -- masses that share the lottery, e.g. the restrictions of one
+ * distribution to G groups of households -- over T periods: every cohort takes
+ * aiy_transition_forward's step, and its mass, K_out and C_out have the bits that call gives on
+ * the cohort alone, whatever G, the cohort's place and the other cohorts are.  One launch per
+ * period carries all cohorts: the index and the weights are read once per period.
+ *   lo / wlo [n_lot][n_cal][S][n_a] device; n_lot = T: period t steps with lottery t; n_lot = 1:
+ *            every period steps with the one lottery (a steady state)
+ *   edges    HOST [n_cal][Q+1]: class q of calibration cal holds the nodes
+ *            [edges[q], edges[q+1]); non-decreasing, edges[0] = 0, edges[Q] = n_a; repeated
+ *            values (empty classes) are allowed
+ *   mass     DEVICE [G][n_cal][S][n_a] (each cohort the [n_cal][S][n_a] of
+ *            aiy_transition_forward): in period 0, out period T
+ *   K_out    HOST [n_cal][G][T+1]: K_g[t] = sum mass_g,t a_grid
+ *   C_out    HOST [n_cal][G][T] or NULL (then R, w, lab may be NULL): aiy_transition_forward's C
+ *   occ_out  HOST [n_cal][G][T+1][Q]: the cohort's mass on the nodes of class q in period t
+ *   inc_out  HOST [n_cal][G][T+1][S] or NULL: the cohort's mass in income state s in period t
+ * occ and inc are sums without atomics whose order depends on (S, n_a, edges) only (DESIGN.md
+ * §4s); period 0 reports the cohorts as given.
+ * Bad sizes (also n_lot not 1 or T), bad edges or a null required buffer: AIY_ERR_ARG before any
+ * launch.  A row of lo that is not non-decreasing or leaves [0, n_a - 2]: AIY_ERR_UNSUPPORTED.
+ * Either way mass and every output stay untouched.  BLOCKING. */
+int32_t aiy_cohort_forward(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T, int32_t n_lot,
+                           int32_t G, int32_t Q, const int32_t* lo, const double* wlo, const double* P,
+                           const double* a_grid, const double* R, const double* w, const double* lab,
+                           const int32_t* edges, void* work, double* mass, double* K_out, double* C_out,
+                           double* occ_out, double* inc_out, aiy_stream stream);
+
 /* ------- sequence-space Jacobian of the household block (build-defined) ------- */
 
 /* The device stages of the fake-news algorithm at a steady state; the backward sweeps are
