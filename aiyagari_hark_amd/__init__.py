@@ -14,7 +14,9 @@ of the household block (``household_jacobian``, ``impulse_response``) in
 :mod:`aiyagari_hark_amd.transition`; the economy with aggregate TFP risk to first order
 (``policy_jacobian``, ``linear_model``, ``simulate``, ``saving_rule``) in
 :mod:`aiyagari_hark_amd.aggregate`; wealth statistics of the panel and of histogram
-distributions and paths (``histogram_stats``, ``batch_wealth_stats``, ``path_wealth_stats``) in
+distributions and paths (``histogram_stats``, ``batch_wealth_stats``, ``path_wealth_stats``) and
+the same statistics of consumption, income, earnings and cash on hand (``variable_stats``,
+``household_variables``, ``batch_inequality``, ``path_variable_stats``) in
 :mod:`aiyagari_hark_amd.stats`; values on the histogram and consumption-equivalent welfare gains
 (``stationary_value``, ``path_value``, ``welfare.welfare``) in :mod:`aiyagari_hark_amd.welfare`;
 cohorts followed through the lotteries and mobility tables (``mobility``, ``cohort_forward``,
@@ -32,14 +34,15 @@ def __getattr__(name):
         from . import model
         return getattr(model, name)
     if name in ("steady_state", "household_block", "solve_transition", "TransitionResult", "household_jacobian",
-                "HouseholdJacobian", "impulse_response", "path_wealth_stats"):
+                "HouseholdJacobian", "impulse_response", "path_wealth_stats", "path_variable_stats"):
         from . import transition
         return getattr(transition, name)
     if name in ("policy_jacobian", "PolicyJacobian", "ar1", "linear_model", "AggregateModel", "moments", "expectations",
                 "simulate", "AggregateSimulation", "saving_rule"):
         from . import aggregate
         return getattr(aggregate, name)
-    if name in ("histogram_stats", "batch_wealth_stats", "WealthStats"):
+    if name in ("histogram_stats", "batch_wealth_stats", "WealthStats", "variable_stats", "household_variables",
+                "batch_inequality", "VariableStats", "Inequality"):
         from . import stats
         return getattr(stats, name)
     if name in ("welfare", "stationary_value", "path_value", "consumption_equivalent", "WelfareResult"):

@@ -28,6 +28,9 @@ AIY_MAX_STATES = 64
 AIY_MAX_COHORTS = 16
 AIY_MAX_CLASSES = 32
 AIY_SOW_DOUBLES = 8
+AIY_VAR_MAX_MOMENTS = 8
+# aiy_household_variables' bit mask, in the order of its output
+AIY_VARIABLES = {"consumption": 1, "income": 2, "earnings": 4, "cash": 8, "saving": 16, "wealth": 32}
 AIY_OPT_USE_GRAPHS = 1
 AIY_OPT_RESIDENT = 2
 AIY_OPT_RESIDENT_SHAPE = 3
@@ -173,6 +176,9 @@ SIGNATURES = {
     "aiy_transition_forward_marginals": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                           ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                           c_double_p, c_double_p, vp, vp]),
+    "aiy_transition_forward_masses": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                       ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                       c_double_p, c_double_p, vp, vp]),
     "aiy_transition_any_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                        ctypes.c_int32]),
     "aiy_transition_forward_any": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -201,6 +207,13 @@ SIGNATURES = {
     "aiy_dist_marginal": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
     "aiy_dist_stats": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, c_double_p,
                                         ctypes.c_int32, vp, c_double_p, c_double_p, c_double_p, vp]),
+    "aiy_var_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "aiy_household_variables": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                 vp, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp]),
+    "aiy_var_merge": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp,
+                                       vp]),
+    "aiy_var_moments": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.POINTER(vp), vp, vp, c_double_p, vp]),
     "aiy_value_work_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "aiy_value_backward": (ctypes.c_int32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -18,7 +18,8 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libaiyagari.so")
 SOURCES = ["api.hip", "index.hip", "egm.hip", "panel_tab.hip", "panel.hip", "panel_block.hip", "panel_resident.hip",
            "hist.hip", "hist_resident.hip", "hist_krylov.hip", "stats.hip", "ge.hip", "ge_resident.hip", "hooks.hip",
-           "transition.hip", "transition_jac.hip", "dist_stats.hip", "welfare.hip", "aggregate.hip", "cohort.hip"]
+           "transition.hip", "transition_jac.hip", "dist_stats.hip", "welfare.hip", "aggregate.hip", "cohort.hip",
+           "var_stats.hip"]
 HEADERS = ["common.h", "internal.h", "panel_common.h", "hist_cluster.h", "egm_common.h", "hist_bicg.h", "ge_search.h",
            "hist_pull.h", "transition_common.h", "carve.h", "owned.h", "hist_scratch.h"]
 ARCH = os.environ.get("AIY_OFFLOAD_ARCH", "gfx950")

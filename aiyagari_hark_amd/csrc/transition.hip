@@ -722,11 +722,14 @@ extern "C" int32_t aiy_transition_backward(aiy_handle* h, const aiy_transition_m
 // mass, [T + 1][n_cal][n_a], one tr_marginal_kernel launch behind the launch that wrote the mass.
 // ANY: aiy_transition_forward_any's -- `work` is tr_any_work's, the check is tr_build_windows and
 // the number of turned rows goes to rows_turned (host, may be null).
+// With `masses` (aiy_transition_forward_masses) also every period's mass, [T + 1][n_cal][S][n_a]: a
+// device-to-device copy of mass_0 and of each period's freshly written buffer; no launch differs.
 template <bool ANY>
 static int32_t tr_forward_sweep(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T, const int32_t* lo,
                                 const double* wlo, const double* P, const double* a_grid, const double* R,
                                 const double* w, const double* lab, void* work, double* mass, double* Ks_out,
-                                double* C_out, double* marg, aiy_stream stream, int32_t* rows_turned = nullptr) {
+                                double* C_out, double* marg, aiy_stream stream, int32_t* rows_turned = nullptr,
+                                double* masses = nullptr) {
   if (!h) return AIY_ERR_ARG;
   int32_t rc = tr_check(h, n_cal, S, n_a, true, T);
   if (rc) return rc;
@@ -761,14 +764,18 @@ static int32_t tr_forward_sweep(aiy_handle* h, int32_t n_cal, int32_t S, int32_t
   A.Kpart = L.kpart;
   A.Cpart = L.cpart;
   const bool with_c = C_out != nullptr;
-  const size_t per_marg = (size_t)n_cal * n_a;
+  const size_t per_marg = (size_t)n_cal * n_a, per_mass = (size_t)n_cal * S * n_a;
   hipLaunchKernelGGL(tr_K0_kernel, dim3(L.nblk, n_cal), dim3(kTrBlock), 0, st, A, (const double*)mass);
   if (marg) tr_launch_marginal(n_cal, S, n_a, mass, marg, st);
+  if (masses) AIY_HIP(h, hipMemcpyAsync(masses, mass, per_mass * sizeof(double), hipMemcpyDeviceToDevice, st));
   for (int t = 0; t < T; ++t) {   // period t reads mass (t even) / alt (t odd)
     const double* src = (t & 1) ? alt : mass;
     double* dst = (t & 1) ? mass : alt;
     launch_fwd<ANY>(A, t, with_c, src, dst, st);
     if (marg) tr_launch_marginal(n_cal, S, n_a, dst, marg + (size_t)(t + 1) * per_marg, st);
+    if (masses)
+      AIY_HIP(h, hipMemcpyAsync(masses + (size_t)(t + 1) * per_mass, dst, per_mass * sizeof(double),
+                                hipMemcpyDeviceToDevice, st));
   }
   const long long n_sum = (long long)(T + 1) * n_cal;
   hipLaunchKernelGGL(tr_sum_kernel, dim3((unsigned)((n_sum + 255) / 256)), dim3(256), 0, st, A, d_Ks,
@@ -799,6 +806,17 @@ extern "C" int32_t aiy_transition_forward_marginals(aiy_handle* h, int32_t n_cal
   if (!marg_out) return fail(h, AIY_ERR_ARG, "null marg_out");
   return tr_forward_sweep<false>(h, n_cal, S, n_a, T, lo, wlo, P, a_grid, R, w, lab, work, mass, Ks_out, C_out,
                                  marg_out, stream);
+}
+
+extern "C" int32_t aiy_transition_forward_masses(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
+                                                 const int32_t* lo, const double* wlo, const double* P,
+                                                 const double* a_grid, const double* R, const double* w,
+                                                 const double* lab, void* work, double* mass, double* Ks_out,
+                                                 double* C_out, double* mass_path_out, aiy_stream stream) {
+  if (!h) return AIY_ERR_ARG;
+  if (!mass_path_out) return fail(h, AIY_ERR_ARG, "null mass_path_out");
+  return tr_forward_sweep<false>(h, n_cal, S, n_a, T, lo, wlo, P, a_grid, R, w, lab, work, mass, Ks_out, C_out,
+                                 nullptr, stream, nullptr, mass_path_out);
 }
 
 extern "C" int32_t aiy_transition_forward_any(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,

@@ -29,6 +29,7 @@ a batch never interact.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 import time
 from dataclasses import dataclass
@@ -110,6 +111,7 @@ class BlockResult:
     c0: torch.Tensor | None
     mass_T: torch.Tensor      # [n_cal][S][n_a] device
     marg: torch.Tensor | None = None   # [T+1][n_cal][n_a] device: the marginal over assets of every period
+    masses: torch.Tensor | None = None   # [T+1][n_cal][S][n_a] device: every period's mass (masses=True)
 
 
 class TransitionBuffers:
@@ -128,6 +130,7 @@ class TransitionBuffers:
         self.c0 = torch.empty((n_cal, S, n_a + 1), dtype=F64, device=dev)
         self.mass = torch.empty((n_cal, S, n_a), dtype=F64, device=dev)
         self.marg = torch.empty((self.T + 1, n_cal, n_a), dtype=F64, device=dev) if marginals else None
+        self.masses = None   # [T+1][n_cal][S][n_a], allocated by household_block(masses=True) only
 
 
 def transition_backward(batch, R, w, m_term, c_term, buffers, export_policy=True, stream=None):
@@ -145,7 +148,7 @@ def transition_backward(batch, R, w, m_term, c_term, buffers, export_policy=True
 
 
 def transition_forward(batch, lo, wlo, mass, T, work, R=None, w=None, want_c=True, stream=None, marg=None,
-                       rows="monotone"):
+                       rows="monotone", mass_path=None):
     """aiy_transition_forward on device lotteries [T][n_cal][S][n_a]: advances ``mass`` in
     place from period 0 to period T and returns (Ks [n_cal][T+1], C [n_cal][T] or None).
     With ``marg`` (device [T+1][n_cal][n_a]) the sweep is aiy_transition_forward_marginals: the
@@ -159,7 +162,11 @@ def transition_forward(batch, lo, wlo, mass, T, work, R=None, w=None, want_c=Tru
     ...)``, and the call returns ``(Ks, C, rows_turned)``, the number of rows with a decreasing
     pair.  It refuses (AIY_ERR_UNSUPPORTED, everything untouched) an entry outside [0, n_a - 2]
     and a row so disordered that its windows hold more than 4 (n_a + 1) sources; on monotone
-    lotteries it gives the bits of the default.  Any other value: ValueError."""
+    lotteries it gives the bits of the default.  Any other value: ValueError.
+
+    With ``mass_path`` (device [T+1][n_cal][S][n_a]) the sweep is aiy_transition_forward_masses: the
+    same results, and mass_path[t] = mass_t, t = 0 .. T, untouched when a row is
+    refused.  It goes with neither ``marg`` nor ``rows="any"``."""
     if rows not in ("monotone", "any"):
         raise ValueError(f"rows must be 'monotone' or 'any', got {rows!r}")
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
@@ -172,6 +179,15 @@ def transition_forward(batch, lo, wlo, mass, T, work, R=None, w=None, want_c=Tru
             Ks.ctypes.data_as(_lib.c_double_p), C.ctypes.data_as(_lib.c_double_p) if want_c else None)
     if marg is not None and (tuple(marg.shape) != (T + 1, n_cal, n_a) or marg.dtype != F64):
         raise ValueError(f"marg must be float64 [T+1][n_cal][n_a] = {(T + 1, n_cal, n_a)}, got {tuple(marg.shape)}")
+    if mass_path is not None:
+        if marg is not None or rows == "any":
+            raise ValueError("mass_path goes with neither marg nor rows='any'")
+        if tuple(mass_path.shape) != (T + 1, n_cal, S, n_a) or mass_path.dtype != F64:
+            raise ValueError(f"mass_path must be float64 [T+1][n_cal][S][n_a] = {(T + 1, n_cal, S, n_a)}, got "
+                             f"{tuple(mass_path.shape)}")
+        h.check(h.lib.aiy_transition_forward_masses(*args, _lib.ptr(mass_path), _lib.stream_ptr(stream)),
+                "aiy_transition_forward_masses")
+        return Ks, C
     if rows == "any":
         need = int(h.lib.aiy_transition_any_work_bytes(n_cal, S, n_a, int(T)))
         if work.numel() * work.element_size() < need:
@@ -190,13 +206,15 @@ def transition_forward(batch, lo, wlo, mass, T, work, R=None, w=None, want_c=Tru
 
 
 def household_block(batch, R, w, m_term, c_term, mass0, want_c=True, export_policy=True, buffers=None, stream=None,
-                    marginals=False):
+                    marginals=False, masses=False):
     """One household-block evaluation on the price paths R, w ([n_cal][T+1], NumPy or device):
     the backward sweep from the terminal policy (m_term, c_term), then the forward sweep from
     mass0 (left unchanged).  Returns BlockResult: Ks[n_cal][T+1], C[n_cal][T] and the device
     lotteries, period-0 policy and final mass (views of ``buffers``: the next evaluation with
     the same buffers overwrites them).  ``marginals=True`` also returns ``marg`` [T+1][n_cal][n_a],
-    the marginal over assets of every period's mass (``path_wealth_stats`` reads it)."""
+    the marginal over assets of every period's mass (``path_wealth_stats`` reads it).
+    ``masses=True`` instead returns ``masses`` [T+1][n_cal][S][n_a], every period's mass
+    (``path_variable_stats`` reads it; 8 S n_a bytes per calibration and period)."""
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     dev = batch.device
     dR, dw = _device(R, dev), _device(w, dev)
@@ -207,18 +225,23 @@ def household_block(batch, R, w, m_term, c_term, mass0, want_c=True, export_poli
         buffers = TransitionBuffers(batch, T, marginals=marginals)
     elif buffers.T != T:
         raise ValueError(f"buffers hold T={buffers.T}, the price paths T={T}")
+    if marginals and masses:
+        raise ValueError("marginals=True and masses=True do not go together: the marginals are sums of the masses")
     if marginals and buffers.marg is None:
         buffers.marg = torch.empty((T + 1, n_cal, n_a), dtype=F64, device=dev)
+    if masses and getattr(buffers, "masses", None) is None:
+        buffers.masses = torch.empty((T + 1, n_cal, S, n_a), dtype=F64, device=dev)
     m_term = _tables(m_term, n_cal, S, n_a)
     c_term = _tables(c_term, n_cal, S, n_a)
     mass0 = _device(mass0, dev)
     transition_backward(batch, dR, dw, m_term, c_term, buffers, export_policy=export_policy, stream=stream)
     buffers.mass.copy_(mass0.reshape(n_cal, S, n_a))
     Ks, C = transition_forward(batch, buffers.lo, buffers.wlo, buffers.mass, T, buffers.work, dR, dw, want_c=want_c,
-                               stream=stream, marg=buffers.marg if marginals else None)
+                               stream=stream, marg=buffers.marg if marginals else None,
+                               mass_path=buffers.masses if masses else None)
     return BlockResult(Ks=Ks, C=C, lo=buffers.lo, wlo=buffers.wlo, m0=buffers.m0 if export_policy else None,
                        c0=buffers.c0 if export_policy else None, mass_T=buffers.mass,
-                       marg=buffers.marg if marginals else None)
+                       marg=buffers.marg if marginals else None, masses=buffers.masses if masses else None)
 
 
 def path_wealth_stats(batch, marg, percentiles=None):
@@ -236,6 +259,43 @@ def path_wealth_stats(batch, marg, percentiles=None):
                               bottom_share=flip(ws.bottom_share), percentiles=ws.percentiles)
 
 
+def path_variable_stats(batch, lo, wlo, R, w, masses, percentiles=None, variables=("consumption",)):
+    """Statistics of household variables in every period of a path: the lotteries ``lo`` / ``wlo``
+    [T][n_cal][S][n_a], the prices ``R``, ``w`` [n_cal][T+1] and the period masses ``masses``
+    [T+1][n_cal][S][n_a] (device, from ``household_block(masses=True)``).  Returns ``(stats,
+    moments)``: ``stats[name]`` a ``stats.VariableStats`` of shape [n_cal][T+1] for every sortable
+    variable named, ``moments[name]`` a dict of mean, std and cv [n_cal][T+1] for every variable
+    named (``saving`` gets moments only).  Period T has no lottery of its own: its consumption and
+    saving take period T - 1's, with the prices of period T.  One variable is on the device at a time."""
+    names = _stats._check_variables(variables)
+    n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
+    dev = batch.device
+    dR, dw = _device(R, dev), _device(w, dev)
+    T = int(lo.shape[0])
+    if tuple(masses.shape) != (T + 1, n_cal, S, n_a) or tuple(dR.shape) != (n_cal, T + 1) or dR.shape != dw.shape:
+        raise ValueError(f"masses {tuple(masses.shape)} and prices {tuple(dR.shape)} do not fit T={T} lotteries")
+    h = _lib.handle(dev.index)
+    flip = lambda x: np.ascontiguousarray(np.swapaxes(x, 0, 1))   # noqa: E731
+    val = torch.empty((T + 1, n_cal, S, n_a), dtype=F64, device=dev)
+    work = _lib.work_space(dev, "var", "", n_dist=(T + 1) * n_cal, S=S, n_a=n_a)
+    stats, moments = {}, {}
+    for name in names:
+        mask = _lib.AIY_VARIABLES[name]
+        _stats._variables_into(batch, lo, wlo, _lib.ptr(dR), _lib.ptr(dw), T + 1, T, mask, val[:T])
+        _stats._variables_into(batch, lo[T - 1], wlo[T - 1], dR.data_ptr() + 8 * T, dw.data_ptr() + 8 * T, T + 1, 1,
+                               mask, val[T:])
+        mom = _stats._moments(h, [val], masses, (T + 1) * n_cal, S, n_a, work)
+        mean, std, cv, _ = _stats._dispersion(mom, 1)
+        moments[name] = {k: flip(x.reshape(T + 1, n_cal)) for k, x in (("mean", mean), ("std", std), ("cv", cv))}
+        if name in _stats._UNSORTABLE:
+            continue
+        vs = _stats.variable_stats(val, masses, percentiles)
+        stats[name] = _stats.VariableStats(**{f.name: (vs.percentiles if f.name == "percentiles" else
+                                                        flip(getattr(vs, f.name)))
+                                              for f in dataclasses.fields(vs)})
+    return stats, moments
+
+
 @dataclass
 class TransitionResult:
     K: np.ndarray            # [n_cal][T+1] capital path (K[:, 0] = sum mass0 a)
@@ -248,10 +308,12 @@ class TransitionResult:
     stats: _stats.WealthStats | None = None   # [n_cal][T+1] wealth statistics of the path (percentiles=)
     welfare: object | None = None             # welfare.WelfareResult of the path against the steady state (welfare=True)
     cohorts: object | None = None             # mobility.CohortPaths of the wealth classes of mass0 (cohorts=)
+    var_stats: dict | None = None             # name -> stats.VariableStats [n_cal][T+1] (variables=)
+    var_moments: dict | None = None           # name -> dict(mean, std, cv) [n_cal][T+1] (variables=)
 
 
 def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=None, m_term=None, c_term=None,
-                     method="damped", jacobian=None, percentiles=None, welfare=False, cohorts=None):
+                     method="damped", jacobian=None, percentiles=None, welfare=False, cohorts=None, variables=None):
     """Equilibrium capital path of every calibration of ``batch`` after the TFP path Z
     ([T+1] or [n_cal][T+1], Z[T] = 1), from the distribution mass0 (default: batch.mass, the
     steady state) to the terminal policy (default: batch.last_tables).
@@ -282,9 +344,20 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
     ``TransitionResult.cohorts``, the ``mobility.CohortPaths`` of the wealth classes of mass0
     between these percentiles (``mobility.wealth_classes``), swept from mass0 on the lotteries and
     prices of the last evaluation: every class's capital and consumption path
-    and its mass by wealth class and income state.  Nothing else of the result changes."""
+    and its mass by wealth class and income state.  Nothing else of the result changes.
+
+    ``variables`` (names out of ``stats.VARIABLES``, with ``percentiles``): also
+    ``TransitionResult.var_stats`` and ``.var_moments``, the ``path_variable_stats`` of the solved
+    path -- one more forward sweep, keeping every period's mass, from mass0 on the
+    lotteries of the last evaluation, exactly as ``percentiles`` alone does for wealth.  Period T
+    has no lottery, so its consumption and saving take period T - 1's.  Without ``variables`` not
+    one call more is made and both fields are None.  Nothing else of the result changes."""
     n_cal, S, n_a = len(batch.cals), batch.S, batch.n_a
     T = int(T)
+    if variables is not None:
+        variables = _stats._check_variables(variables)
+        if percentiles is None:
+            raise ValueError("variables= needs percentiles=")
     if method not in ("damped", "newton"):
         raise ValueError(f"method must be 'damped' or 'newton', got {method!r}")
     if method == "damped" and jacobian is not None:
@@ -344,6 +417,14 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
         marg = torch.empty((T + 1, n_cal, n_a), dtype=F64, device=batch.device)
         transition_forward(batch, buffers.lo, buffers.wlo, buffers.mass, T, buffers.work, want_c=False, marg=marg)
         path_stats = path_wealth_stats(batch, marg, percentiles)
+    var_stats = var_moments = None
+    if variables is not None:
+        buffers.mass.copy_(mass0)
+        masses = torch.empty((T + 1, n_cal, S, n_a), dtype=F64, device=batch.device)
+        transition_forward(batch, buffers.lo, buffers.wlo, buffers.mass, T, buffers.work, want_c=False,
+                           mass_path=masses)
+        var_stats, var_moments = path_variable_stats(batch, buffers.lo, buffers.wlo, 1.0 + r, w, masses, percentiles,
+                                                     variables)
     gains = None
     if welfare:
         from . import welfare as _welfare
@@ -356,7 +437,8 @@ def solve_transition(batch, Z, T, damping=0.5, tol=1e-9, max_iter=100, mass0=Non
         followed = _mobility.cohort_forward(batch, buffers.lo, buffers.wlo,
                                             _mobility.cohorts_by_class(batch, edges, mass=mass0), T, edges, R=1.0 + r, w=w)
     return TransitionResult(K=K, r=r, w=w, C=C, iterations=iterations, residual=residual, status=status,
-                            stats=path_stats, welfare=gains, cohorts=followed)
+                            stats=path_stats, welfare=gains, cohorts=followed, var_stats=var_stats,
+                            var_moments=var_moments)
 
 
 def steady_rate(batch):

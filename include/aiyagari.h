@@ -598,6 +598,19 @@ int32_t aiy_transition_forward_marginals(aiy_handle* h, int32_t n_cal, int32_t S
                                          void* work, double* mass, double* Ks_out, double* C_out, double* marg_out,
                                          aiy_stream stream);
 
+/* aiy_transition_forward, which also keeps every period's mass:
+ *   mass_path_out DEVICE [T+1][n_cal][S][n_a] (caller-owned): mass_0 and the buffer every period's
+ *                 step just wrote, by device-to-device copies enqueued behind the launches (8 S
+ *                 bytes per node and period; 4.05 GB at 24 x 7 x 10 000 nodes and T = 300).
+ * No kernel differs: mass, Ks_out and C_out have the bits of the plain sweep; the row check, the
+ * argument checks and the blocking are its own, and a failed row check leaves mass_path_out
+ * untouched too.  `work` is aiy_transition_work_bytes', unchanged. */
+int32_t aiy_transition_forward_masses(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t T,
+                                      const int32_t* lo, const double* wlo, const double* P,
+                                      const double* a_grid, const double* R, const double* w, const double* lab,
+                                      void* work, double* mass, double* Ks_out, double* C_out,
+                                      double* mass_path_out, aiy_stream stream);
+
 /* Device scratch of aiy_transition_forward_any: the regions of aiy_transition_work_bytes, then the
  * second window array ([T][n_cal][S][n_a + 1] int32) and the check's counters; -1 for the same
  * bad sizes.  A work space of this size also serves aiy_transition_backward.  Host-only. */
@@ -774,6 +787,69 @@ int32_t aiy_dist_marginal(aiy_handle* h, int32_t n_dist, int32_t S, int32_t n_a,
 int32_t aiy_dist_stats(aiy_handle* h, int32_t n_dist, int32_t n_grid, int32_t n_a, const double* g,
                        const double* a_grid, const double* pctiles, int32_t n_p, void* work, double* lorenz_out,
                        double* pctl_out, double* summary_out, aiy_stream stream);
+
+/* ------- statistics of any household variable (build-defined) ------- */
+
+/* The variables of a node (s, j) of a period with lottery (lo, wlo) and prices (R, w), a' the
+ * lottery's savings wlo a[lo] + (1 - wlo) a[lo + 1] (lo read as held to [0, n_a - 2]):
+ *   consumption  (R a_j + w lab_s) - a'        (c_t[s][j] of the welfare section below)
+ *   income       (R - 1) a_j + w lab_s
+ *   earnings     w lab_s
+ *   cash         R a_j + w lab_s
+ *   saving       a' - a_j
+ *   wealth       a_j
+ * each with the operations of the expression as written (the NumPy expressions' bits). */
+#define AIY_VAR_CONSUMPTION 1
+#define AIY_VAR_INCOME 2
+#define AIY_VAR_EARNINGS 4
+#define AIY_VAR_CASH 8
+#define AIY_VAR_SAVING 16
+#define AIY_VAR_WEALTH 32
+#define AIY_VAR_MAX_MOMENTS 8
+
+/* Device scratch of aiy_var_merge and aiy_var_moments for n_dist distributions (the check's flag
+ * and the moments of every distribution), -1 for n_dist < 1, n_a < 2, S outside
+ * 1..AIY_MAX_STATES or S n_a >= 2^31.  Host-only. */
+int64_t aiy_var_work_bytes(int32_t n_dist, int32_t S, int32_t n_a);
+
+/* The variables named by the bit mask `which` (AIY_VAR_*), element by element, no atomics:
+ *   lo / wlo  [n_t][n_cal][S][n_a] (may be NULL unless consumption or saving is asked for)
+ *   R / w     DEVICE, period t of calibration cal at [cal * ld_price + t], ld_price >= n_t
+ *   a_grid    [n_cal][n_a]; lab [n_cal][S]
+ *   out       DEVICE: the variables asked for in ascending bit order, each [n_t][n_cal][S][n_a]
+ * Asynchronous. */
+int32_t aiy_household_variables(aiy_handle* h, int32_t n_cal, int32_t S, int32_t n_a, int32_t n_t,
+                                const int32_t* lo, const double* wlo, const double* R, const double* w,
+                                int32_t ld_price, const double* a_grid, const double* lab, int32_t which,
+                                double* out, aiy_stream stream);
+
+/* Orders every distribution of a stack whose S rows are each nondecreasing: an S-way merge.
+ *   key / weight               DEVICE [n_dist][S][n_a]
+ *   key_sorted / weight_sorted DEVICE [n_dist][S n_a]: the order of
+ *                              np.argsort(key.reshape(-1), kind="stable"), by key, ties by (s, j)
+ *   rank_out                   DEVICE int32 [n_dist][S][n_a] or NULL: the place of (s, j), j plus,
+ *                              for every other row s', its entries with key <= y (s' < s) or
+ *                              key < y (s' > s)
+ *   work                       DEVICE, aiy_var_work_bytes(n_dist, S, n_a)
+ * Every output element is a copy of an input element: the same bits in every run, alone or in a
+ * stack.  No atomics, no sort.  A first pass checks that every row is nondecreasing and free of
+ * NaN; AIY_ERR_UNSUPPORTED with nothing written if one is not.  AIY_ERR_ARG for bad sizes or a
+ * null buffer, before any launch.  Blocks for the check's flag; the merge itself is enqueued. */
+int32_t aiy_var_merge(aiy_handle* h, int32_t n_dist, int32_t S, int32_t n_a, const double* key,
+                      const double* weight, void* work, double* key_sorted, double* weight_sorted,
+                      int32_t* rank_out, aiy_stream stream);
+
+/* Weighted moments of n_v <= AIY_VAR_MAX_MOMENTS variables on one weight stack, one launch, two
+ * passes (means, then centred products; not sum w y^2 - m^2); the rows need not be monotone.
+ *   vars   HOST array of n_v DEVICE pointers, each [n_dist][S][n_a]; weight DEVICE, the same shape
+ *   work   DEVICE, aiy_var_work_bytes(n_dist, S, n_a)
+ *   out    HOST [n_dist][1 + n_v + n_v n_v]: sum w, the means m_u = sum w y_u / sum w, then
+ *          sum w (y_u - m_u)(y_v - m_v) / sum w at [1 + n_v + u n_v + v]
+ * Sum order: a row (d, s) in contiguous chunks of ceil(n_a / 256) nodes reduced as
+ * aiy_dist_stats reduces its Gini terms, then the rows in ascending s.  BLOCKING. */
+int32_t aiy_var_moments(aiy_handle* h, int32_t n_dist, int32_t S, int32_t n_a, int32_t n_v,
+                        const double* const* vars, const double* weight, void* work, double* out,
+                        aiy_stream stream);
 
 /* ---- welfare: values on the histogram and consumption equivalents (build-defined) ---- */
 
