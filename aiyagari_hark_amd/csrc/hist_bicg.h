@@ -2,6 +2,11 @@
 // Krylov mode) as a device function: hist_krylov.hip runs one solve per launch,
 // ge_resident.hip many solves per launch inside its device-resident GE search.
 // See hist_krylov.hip for the algorithm.
+// A lottery that is not "monotone, of ours" stops the cluster with error 2 before the first
+// matvec, in both forms and from every entry: the pull form needs every row non-decreasing
+// inside the grid; the push form needs every own entry of a workgroup inside the grid and inside
+// the bracket [lo(j0), lo(j1 - 1)] of its row's end columns (neighbours that swap order inside
+// the bracket are harmless to a push and run).
 #pragma once
 
 #include "common.h"
@@ -290,6 +295,12 @@ __device__ __forceinline__ int hk_solve(const HkArgs& r, const HkShared<SMAX, KC
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   if (!PULL) {
+  // every own entry, not only the two end columns (as hist_cluster_kernel): inside the grid
+  // and inside [lo(j0), lo(j1 - 1)] of its row, or error 2 -- no push leaves its row's span
+  if (!hc_own_in_bracket<KC, TH>(LO, S, n_a, j0, j1)) {
+    __hip_atomic_store(to_global(err), 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
   if (!barrier()) return -1;
   if (hc_failed(err, &s_stop)) return -1;
   if (tid < S) {

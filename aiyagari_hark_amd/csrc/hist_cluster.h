@@ -152,6 +152,35 @@ __device__ __forceinline__ bool hc_failed(const unsigned* err, int* s_stop) {
   return *s_stop != 0;
 }
 
+// Push forms: whether every own lottery entry of this workgroup (columns [j0, j1), thread t owns
+// j0 + t + k TH, k < KC) lies inside the grid and inside the bracket [lo(j0), lo(j1 - 1)] of its
+// row's end columns, for which the spans are laid out: an entry beyond it would add into another
+// row's span or behind the span buffer.  Once per solve, before the first cluster barrier.  Eight
+// rows' loads are issued before the first compare (indices clamped to the last own column and the
+// last state: the same entries again, no predicate), the flags combined without branches.
+template <int KC, int TH>
+__device__ __forceinline__ bool hc_own_in_bracket(const int* LO, int S, int n_a, int j0, int j1) {
+  constexpr int R = 8;
+  int bad = 0;
+  for (int s0 = 0; s0 < S; s0 += R) {
+    int l[R][KC], f[R], fl[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const int* Ls = LO + (size_t)min(s0 + u, S - 1) * n_a;
+      f[u] = Ls[j0];
+      fl[u] = Ls[j1 - 1];
+#pragma unroll
+      for (int k = 0; k < KC; ++k) l[u][k] = Ls[min(j0 + (int)threadIdx.x + k * TH, j1 - 1)];
+    }
+#pragma unroll
+    for (int u = 0; u < R; ++u)
+#pragma unroll
+      for (int k = 0; k < KC; ++k)
+        bad |= (int)(l[u][k] < f[u]) | (int)(l[u][k] > fl[u]) | (int)(l[u][k] < 0) | (int)(l[u][k] > n_a - 2);
+  }
+  return bad == 0;
+}
+
 // ---- cluster reduction ----
 // Cluster-wide reduction of nv <= kHcRed per-thread values (bit v of kmax: nan_max, else sum),
 // fixed order at every level, so every workgroup gets the same s_res: lanes by

@@ -27,7 +27,10 @@
 // no global atomics, one barrier.
 // Shapes that do not fit (spans beyond the LDS budget, more covering workgroups per row
 // than kHcCand, a non-monotone lottery) abort before the first iteration and the host
-// runs the push/mix pair instead.
+// runs the push/mix pair instead.  "Non-monotone" is decided per workgroup from every own
+// entry: one outside the grid's [0, n_a - 2] or outside [lo(j0), lo(j1 - 1)] of its row is
+// refused (error 2), so no push leaves its row's span; neighbours that swap order inside
+// that bracket are harmless to the push and run.
 #include "common.h"
 #include "internal.h"
 #include "hist_cluster.h"
@@ -123,6 +126,14 @@ __global__ __launch_bounds__(TH) void hist_cluster_kernel(HcRun r) {
     s_tot = tot;
     if (tot > cap) bad = 2u;
     if (bad) __hip_atomic_store(to_global(r.err), bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  // every own entry, not only the two end columns: inside the grid and inside the bracket
+  // [lo(j0), lo(j1 - 1)] the spans were laid out for (an interior entry beyond it would add
+  // into another row's span or behind the span buffer).  Once per solve; a thread that finds
+  // one sets the error word, the barrier below carries it to the cluster.
+  if (!hc_own_in_bracket<KC, TH>(LO, S, n_a, j0, j1)) {
+    __hip_atomic_store(to_global(r.err), 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   double m[KC][SMAX];
