@@ -1,10 +1,78 @@
-// Handle lifecycle, errors and the RCCL binding of libaiyagari.
+// Handle lifecycle, options, errors and the RCCL binding of libaiyagari.
 #include "internal.h"
 
 #include <cstring>
 #include <new>
 
 extern "C" int32_t aiy_version(void) { return 210; }  // 0.2.1: Krusell-Smith employment
+
+// Every handle option once: id, name, field, default and the values it takes.  aiy_set_option,
+// aiy_get_option and the handle's defaults all read this table.
+namespace {
+enum class Takes { flag, range, zero_or_range };   // flag: any nonzero value is 1
+struct Option {
+  int32_t id;
+  const char* name;
+  int aiy_handle::*field;
+  int def; Takes takes; int64_t lo, hi;
+};
+#define AIY_FLAG(NAME, field, def) {AIY_OPT_##NAME, "AIY_OPT_" #NAME, &aiy_handle::field, def, Takes::flag, 0, 1}
+#define AIY_RANGE(NAME, field, def, lo, hi) {AIY_OPT_##NAME, "AIY_OPT_" #NAME, &aiy_handle::field, def, Takes::range, lo, hi}
+const Option kOptions[] = {
+    AIY_FLAG(USE_GRAPHS, use_graphs, 1),
+    AIY_FLAG(RESIDENT, use_resident, 1),
+    AIY_RANGE(RESIDENT_SHAPE, res_shape, 0, 0, 2),
+    AIY_FLAG(HIST_FUSED, hist_fused, 0),
+    AIY_FLAG(RESIDENT_STREAM, res_stream, 0),
+    AIY_FLAG(HIST_RESIDENT, hist_resident, 1),
+    AIY_RANGE(HIST_CLUSTER, hist_cluster_cap, 0, 0, 128),
+    AIY_RANGE(HIST_ACCEL, hist_accel, 0, 0, 1 << 20),
+    AIY_FLAG(HIST_KRYLOV, hist_krylov, 0),
+    AIY_FLAG(GE_RESIDENT, ge_resident, 0),
+    AIY_RANGE(CU_LIMIT, cu_limit, 0, 0, 65536),
+    AIY_RANGE(GE_REBALANCE, ge_rebalance, 55, 0, 100),
+    AIY_RANGE(GE_EXTRAP_PERIOD, ge_extrap_period, 32, 4, 1024),
+    AIY_RANGE(GE_LOGSEC, ge_logsec, 2, 0, 2),
+    AIY_FLAG(HIST_PULL, hist_pull, 0),
+    AIY_RANGE(GE_LOOSE_HIST, ge_loose_hist, 8, 6, 14),
+    AIY_RANGE(RESIDENT_SHAPE_STREAM, res_shape_stream, 1, -1, 2),
+    {AIY_OPT_GE_ANDERSON, "AIY_OPT_GE_ANDERSON", &aiy_handle::ge_anderson, 12, Takes::zero_or_range, 5, 1024},
+    AIY_FLAG(HIST_IID, hist_iid, 1),
+};
+#undef AIY_FLAG
+#undef AIY_RANGE
+
+const Option* find_option(aiy_handle* h, int32_t id) {
+  for (const Option& o : kOptions)
+    if (o.id == id) return &o;
+  aiy::fail(h, AIY_ERR_ARG, "unknown option %d", id);
+  return nullptr;
+}
+}  // namespace
+
+aiy_handle::aiy_handle() { for (const Option& o : kOptions) this->*o.field = o.def; }
+
+extern "C" int32_t aiy_set_option(aiy_handle* h, int32_t option, int64_t value) {
+  if (!h) return AIY_ERR_ARG;
+  const Option* o = find_option(h, option);
+  if (!o) return AIY_ERR_ARG;
+  if (o->takes == Takes::flag) value = value != 0;
+  else if ((value < o->lo || value > o->hi) && !(o->takes == Takes::zero_or_range && value == 0))
+    return aiy::fail(h, AIY_ERR_ARG, "%s must be %sin [%lld, %lld]", o->name,
+                     o->takes == Takes::zero_or_range ? "0 or " : "", (long long)o->lo, (long long)o->hi);
+  h->*o->field = (int)value;
+  return AIY_OK;
+}
+
+// Current value of a handle option (the values aiy_set_option takes), so callers can save
+// and restore what they change.
+extern "C" int32_t aiy_get_option(aiy_handle* h, int32_t option, int64_t* value) {
+  if (!h || !value) return AIY_ERR_ARG;
+  const Option* o = find_option(h, option);
+  if (!o) return AIY_ERR_ARG;
+  *value = h->*o->field;
+  return AIY_OK;
+}
 
 extern "C" int32_t aiy_create(int32_t device, aiy_handle** out) {
   if (!out) return AIY_ERR_ARG;

@@ -23,10 +23,7 @@ __global__ void hook_shocks_kernel(int n_lab, const double* __restrict__ cdf, lo
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double uu = u ? u[i] : philox_uniform(ctr0, (uint64_t)(offset + i), seed, 0u);
-  const int l0 = lab[i];
-  int l = 0;
-  for (int q = 0; q < n_lab; ++q) l += (cdf[l0 * n_lab + q] <= uu) ? 1 : 0;
-  lab[i] = (uint8_t)l;
+  lab[i] = (uint8_t)draw_labour(cdf, n_lab, lab[i], uu);
 }
 
 // get_states (AS:1276-1283): m = Rnow a_prev + Wnow LSStates[l] Emp
@@ -35,18 +32,24 @@ __global__ void hook_states_kernel(const double* __restrict__ lvl, long long n, 
                                    const uint8_t* __restrict__ emp, double* __restrict__ m_out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double e = emp ? (double)emp[i] : 1.0;
-  m_out[i] = R * a_prev[i] + W * (lvl[lab[i]] * e);
+  m_out[i] = cash_on_hand(R, W, a_prev[i], lvl[lab[i]], emp ? (double)emp[i] : 1.0);
 }
 
 // get_controls (AS:1295-1408): c = cFunc[4 l + 2 Mrkv + Emp](m, Mnow), HARK's
 // LinearInterpOnInterp1D over the raw policy tables (the M bracket is the period's).
-__global__ void hook_controls_kernel(int n_M, int n_a, const double* __restrict__ m_tab,
-                                     const double* __restrict__ c_tab, int jc, double alpha, int Mrkv, long long n,
-                                     const double* __restrict__ m, const uint8_t* __restrict__ lab,
-                                     const uint8_t* __restrict__ emp, double* __restrict__ c_out) {
+struct RawPolicy {
+  int n_M, n_a;
+  const double *m_tab, *c_tab;
+  int jc, Mrkv;   // the period's M bracket and aggregate state
+  double alpha;
+};
+__global__ void hook_controls_kernel(RawPolicy pol, long long n, const double* __restrict__ m,
+                                     const uint8_t* __restrict__ lab, const uint8_t* __restrict__ emp,
+                                     double* __restrict__ c_out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  const int n_M = pol.n_M, n_a = pol.n_a, jc = pol.jc, Mrkv = pol.Mrkv;
+  const double *m_tab = pol.m_tab, *c_tab = pol.c_tab, alpha = pol.alpha;
   const int e = emp ? (int)emp[i] : 1;
   const int s = 4 * (int)lab[i] + 2 * Mrkv + e;
   const int n1 = n_a + 1;
@@ -75,9 +78,7 @@ __global__ __launch_bounds__(1024) void hook_sum_kernel(long long n, const doubl
   __shared__ double red[1024 / kWave];
   double acc = 0.0;
   for (long long i = threadIdx.x; i < n; i += blockDim.x) acc += x[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = acc;
+  wave_partials(acc, red);
   __syncthreads();
   if (threadIdx.x == 0) {
     double s = 0.0;
@@ -142,8 +143,8 @@ extern "C" int32_t aiy_get_controls(aiy_handle* h, int32_t S, int32_t n_M, int32
     jc = j - 1;
   }
   AIY_HIP(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(hook_controls_kernel, dim3(hook_blocks(n)), dim3(kHookBlock), 0, as_stream(stream), n_M, n_a,
-                     m_tab, c_tab, jc, alpha, Mrkv, (long long)n, m, lab, emp, c_out);
+  hipLaunchKernelGGL(hook_controls_kernel, dim3(hook_blocks(n)), dim3(kHookBlock), 0, as_stream(stream),
+                     RawPolicy{n_M, n_a, m_tab, c_tab, jc, Mrkv, alpha}, (long long)n, m, lab, emp, c_out);
   AIY_CHECK_LAUNCH(h);
   return AIY_OK;
 }

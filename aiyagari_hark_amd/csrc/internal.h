@@ -16,7 +16,9 @@
 
 // Every allocation and event of the handle is an owning type of owned.h, grown by reserve()
 // where it is used; a buffer of several arrays is carved by its user's layout function (carve.h).
+// The AIY_OPT_* fields get their defaults from the option table (api.hip) in the constructor.
 struct aiy_handle {
+  aiy_handle();
   int device = 0;
   std::string err;
   // EGM convergence bookkeeping (egm.hip, EgmSlots): distance slots (bit patterns of non-negative
@@ -29,19 +31,19 @@ struct aiy_handle {
   // panel: per-block partial sums and the last-block-done counter of the period kernel
   aiy::DeviceBuffer partials, ticket;
   hipStream_t cap_stream = nullptr;  // hipGraph capture stream
-  bool use_graphs = true;
+  int use_graphs;                    // AIY_OPT_USE_GRAPHS
   // histogram (hist.hip, HistSlots): per-calibration sup-norm slots [n_cal][3], sums of K
   // (+ partials), last iteration (+ monotone flag); device and pinned host mirror
   aiy::DeviceBuffer hist_dev; aiy::PinnedBuffer hist_pin;
-  bool hist_fused = false;           // AIY_OPT_HIST_FUSED
-  bool hist_resident = true;         // AIY_OPT_HIST_RESIDENT (hist_resident.hip)
-  int hist_cluster_cap = 0;          // AIY_OPT_HIST_CLUSTER: max workgroups per calibration (0: 32)
-  int hist_accel = 0;                // AIY_OPT_HIST_ACCEL: Aitken period of the resident histogram (0: off)
-  int hist_krylov = 0;               // AIY_OPT_HIST_KRYLOV: resident histogram solves by BiCGSTAB
-  int res_shape_stream = 1;          // AIY_OPT_RESIDENT_SHAPE_STREAM: shape of the HBM-streaming form (-1: res_shape)
-  int hist_pull = 0;                 // AIY_OPT_HIST_PULL: BiCGSTAB matvecs of S <= 8 by the lottery pull
-  int hist_iid = 1;                  // AIY_OPT_HIST_IID: i.i.d.-income cells of the resident search collapse the income dimension
-  int ge_loose_hist = 8;             // AIY_OPT_GE_LOOSE_HIST: loose-bracketing histogram tolerance 10^-value
+  int hist_fused;                    // AIY_OPT_HIST_FUSED
+  int hist_resident;                 // AIY_OPT_HIST_RESIDENT (hist_resident.hip)
+  int hist_cluster_cap;              // AIY_OPT_HIST_CLUSTER: max workgroups per calibration (0: 32)
+  int hist_accel;                    // AIY_OPT_HIST_ACCEL: Aitken period of the resident histogram (0: off)
+  int hist_krylov;                   // AIY_OPT_HIST_KRYLOV: resident histogram solves by BiCGSTAB
+  int res_shape_stream;              // AIY_OPT_RESIDENT_SHAPE_STREAM: shape of the HBM-streaming form (-1: res_shape)
+  int hist_pull;                     // AIY_OPT_HIST_PULL: BiCGSTAB matvecs of S <= 8 by the lottery pull
+  int hist_iid;                      // AIY_OPT_HIST_IID: i.i.d.-income cells of the resident search collapse the income dimension
+  int ge_loose_hist;                 // AIY_OPT_GE_LOOSE_HIST: loose-bracketing histogram tolerance 10^-value
   // per-calibration tolerances for one call (aiy_ge_stationary's loose bracketing); null: the
   // scalar tolerance of the call.  Device arrays [n_cal]; egm_tolh: the host copy.
   const double* egm_tolv = nullptr;
@@ -53,15 +55,15 @@ struct aiy_handle {
   aiy::DeviceBuffer hc, hcd;
   aiy::LaunchTimer hc_timer;         // aiy_hist_launch_stats
   // device-resident GE search (ge_resident.hip)
-  bool ge_resident = false;          // AIY_OPT_GE_RESIDENT
-  int cu_limit = 0;                  // AIY_OPT_CU_LIMIT: compute units resident launches may fill (0: all)
-  int ge_rebalance = 55;             // AIY_OPT_GE_REBALANCE: % finished that stops a launch (0: one launch)
+  int ge_resident;                   // AIY_OPT_GE_RESIDENT
+  int cu_limit;                      // AIY_OPT_CU_LIMIT: compute units resident launches may fill (0: all)
+  int ge_rebalance;                  // AIY_OPT_GE_REBALANCE: % finished that stops a launch (0: one launch)
   int ge_rounds = 0;                 // launches of the last device-resident search
   int ge_mid_stops = 0;              // of its clusters, those stopped inside a distribution solve
   int ge_iid_cells = 0;              // of its calibrations, those whose distribution solves ran on the asset grid
-  int ge_extrap_period = 32;         // AIY_OPT_GE_EXTRAP_PERIOD: EGM cycles between extrapolation checks
-  int ge_anderson = 12;              // AIY_OPT_GE_ANDERSON: EGM cycles between Anderson mixes (0: off)
-  int ge_logsec = 2;                 // AIY_OPT_GE_LOGSEC: 0 off, 1 two-point log-secant bracketing, 2 also from one point (with loose bracketing)
+  int ge_extrap_period;              // AIY_OPT_GE_EXTRAP_PERIOD: EGM cycles between extrapolation checks
+  int ge_anderson;                   // AIY_OPT_GE_ANDERSON: EGM cycles between Anderson mixes (0: off)
+  int ge_logsec;                     // AIY_OPT_GE_LOGSEC: 0 off, 1 two-point log-secant bracketing, 2 also from one point (with loose bracketing)
   aiy::DeviceBuffer ge;              // tables, masses, lottery, cluster sync of the launch (GeScratch)
   aiy::LaunchTimer ge_timer;         // aiy_ge_launch_stats
   double ge_points = 0.0, ge_egm_cycles = 0.0;
@@ -72,16 +74,17 @@ struct aiy_handle {
   aiy::DeviceBuffer cohort;          // cohorts (cohort.hip): K, C, occ and inc of every period (CoSums)
   // resident panel: tagged partial-sum granules + timeout word; option
   aiy::DeviceBuffer res_sync;
-  bool use_resident = true;
-  int res_shape = 0;                 // resident workgroup shape (AIY_OPT_RESIDENT_SHAPE)
+  int use_resident;                  // AIY_OPT_RESIDENT
+  int res_shape;                     // resident workgroup shape (AIY_OPT_RESIDENT_SHAPE)
   aiy::LaunchTimer res_timer;        // brackets every resident launch (aiy_panel_launch_stats)
   long long res_periods = 0;
   unsigned res_epoch = 0;            // granule tag base of the next resident launch
   const void* res_occ_fn = nullptr;  // resident shape whose occupancy was last checked
   size_t res_occ_lds = 0;
+  bool res_attr_set = false, blk_attr_set = false;   // dynamic-LDS limits raised on this handle's device
   // block panel: per-calibration markets + seeds (device + pinned staging)
   aiy::DeviceBuffer blk_dev; aiy::PinnedBuffer blk_pin;
-  bool res_stream = false;           // AIY_OPT_RESIDENT_STREAM
+  int res_stream;                    // AIY_OPT_RESIDENT_STREAM
   // RCCL
   ncclComm_t comm = nullptr;
   bool comm_owned = false;           // created by aiy_comm_init (destroyed with the handle)

@@ -34,23 +34,21 @@ constexpr int kTicketGroups = 16;
 constexpr int kTicketStride = 32;   // uints: 128 B apart
 constexpr int kGraphPeriods = 64;
 
+// One call's agents, shocks and outputs: an entry point names what it was given, check_run holds
+// it to the checks the entry points share and bind_run adds the handle's scratch.
 struct PanelRun {
-  long long n, offset, n_total;
-  double* a;
-  uint8_t* lab;
-  const double* u;   // uniforms [.. ][u_ld] starting at period u_t0, or nullptr (Philox)
-  long long u_ld;
-  int u_t0;
-  const uint8_t* emp;   // employment [..][emp_ld] from period u_t0, or nullptr (all employed)
-  long long emp_ld;
-  unsigned long long seed;
-  unsigned ge_iter;
-  double* sow;
-  double* partials;
-  unsigned* ticket;
-  double* hist_A;
-  double* hist_M;
-  int finish;        // 1: last block computes prices (single rank); 0: publish local sum only
+  long long n = 0, offset = 0, n_total = 0;
+  double* a = nullptr; uint8_t* lab = nullptr;
+  const double* u = nullptr;   // uniforms [.. ][u_ld] starting at period u_t0, or nullptr (Philox)
+  long long u_ld = 0;
+  int u_t0 = 0;
+  const uint8_t* emp = nullptr;   // employment [..][emp_ld] from period u_t0, or nullptr (all employed)
+  long long emp_ld = 0;
+  unsigned long long seed = 0; unsigned ge_iter = 0;
+  double* sow = nullptr;
+  double* partials = nullptr; unsigned* ticket = nullptr;   // the handle's scratch (bind_run)
+  double* hist_A = nullptr; double* hist_M = nullptr;
+  int finish = 0;    // 1: last block computes prices (single rank); 0: publish local sum only
 };
 
 // calc_R_and_W (AS:1839-1894) given the sum of end-of-period assets over all agents.
@@ -58,13 +56,7 @@ __device__ __forceinline__ void mill(const aiy_market& mk, const int* mrkv_hist,
                                      double* sow, double* hist_A, double* hist_M) {
   const int t = (int)load_f64_agent(&sow[7]);
   const Prices p = calc_prices(mk, mrkv_hist[t], sum_a / (double)n_total);   // np.mean(np.array(aNow))
-  store_f64_agent(&sow[0], p.Mnow);
-  store_f64_agent(&sow[1], p.Aprev);
-  store_f64_agent(&sow[2], (double)p.Mrkv);
-  store_f64_agent(&sow[3], p.Rnow);
-  store_f64_agent(&sow[4], p.Wnow);
-  store_f64_agent(&sow[5], 0.0);  // Urate is recorded by the caller (it draws the employment)
-  store_f64_agent(&sow[7], (double)(t + 1));
+  store_sow(sow, p, t + 1);
   if (hist_A) hist_A[t] = p.Aprev;
   if (hist_M) hist_M[t] = p.Mnow;
 }
@@ -96,6 +88,7 @@ __global__ __launch_bounds__(kSimBlock) void sim_period_kernel(PanelDev P, Panel
   }
   __syncthreads();
   double local = 0.0;
+  // (the step is agent_step's, panel_common.h, written out: see the note there)
   // kPairs agent PAIRS per lane (one Philox call and one 16-byte asset load per pair),
   // their dependent chains interleaved: the panel is latency-bound, and this puts the
   // whole population in flight in one wave round.
@@ -165,9 +158,7 @@ __global__ __launch_bounds__(kSimBlock) void sim_period_kernel(PanelDev P, Panel
   // ---- block partial, then the last block finishes the period ----
   __shared__ double red[kSimBlock / kWave];
   __shared__ int is_last;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, kWave);
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = local;
+  wave_partials(local, red);
   __syncthreads();
   if (threadIdx.x == 0) {
     // Hand-off without fences (MI355X_MICROARCH.md, "Valid forms", row 1): the partial is
@@ -194,10 +185,7 @@ __global__ __launch_bounds__(kSimBlock) void sim_period_kernel(PanelDev P, Panel
   if (!is_last) return;
   double acc = 0.0;
   for (int b = threadIdx.x; b < (int)gridDim.x; b += blockDim.x) acc += load_f64_agent(&r.partials[b]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
-  __syncthreads();
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = acc;
+  wave_partials(acc, red);
   __syncthreads();
   if (threadIdx.x == 0) {
     const double total = (red[0] + red[1]) + (red[2] + red[3]);
@@ -257,6 +245,48 @@ static int32_t enqueue_period(aiy_handle* h, const PanelDev& P, const PanelRun& 
   return AIY_OK;
 }
 
+// May this call take the resident kernel (panel_resident.hip)?  Every condition in one place.
+static bool resident_eligible(const aiy_handle* h, const PanelDev& P, long long n, const double* a, const uint8_t* lab,
+                              const uint8_t* emp, long long agent_offset, bool sharded) {
+  return h->use_resident &&
+         !emp &&   // it simulates the employed sub-states only (Krusell-Smith mode runs the per-period kernel)
+         n >= kResMinAgents && resident_supported(P) && resident_aligned(a, lab) &&
+         // sharded: its Philox pairs (2k, 2k + 1) must not straddle shards; single rank: its
+         // instantiations without the shard code draw at offset 0
+         (sharded ? (agent_offset & 1) == 0 : agent_offset == 0);
+}
+
+// The checks the entry points share: agent counts, agent arrays, ge_iter, employment versus tables.
+static int32_t check_run(aiy_handle* h, const PanelDev& P, const PanelRun& r) {
+  if (r.n < 0 || r.offset < 0) return fail(h, AIY_ERR_ARG, "bad agent counts");
+  if (r.n > 0 && (!r.a || !r.lab)) return fail(h, AIY_ERR_ARG, "null agent arrays");
+  if (r.emp && !P.unemployed) return fail(h, AIY_ERR_ARG, "employment states need tables with the unemployed cells");
+  if (r.ge_iter >= (1u << 12)) return fail(h, AIY_ERR_ARG, "ge_iter too large for the Philox counter");
+  return AIY_OK;
+}
+
+// The handle's device, scratch (into r) and stream hand-off, then period t0 in sow[7].
+static int32_t bind_run(aiy_handle* h, PanelRun& r, int t0, hipStream_t st) {
+  AIY_HIP(h, hipSetDevice(h->device));
+  int32_t rc = ensure_panel_scratch(h);
+  if (rc == AIY_OK) rc = use_stream(h, st);
+  if (rc) return rc;
+  r.partials = h->partials.as<double>();
+  r.ticket = h->ticket.as<unsigned>();
+  hipLaunchKernelGGL(set_period_kernel, dim3(1), dim3(64), 0, st, r.sow, t0);
+  return AIY_OK;
+}
+
+// The resident launch of periods [t0, t0 + n_periods) of a run.
+static ResRun resident_run(const PanelRun& r, int t0, int n_periods, int flags) {
+  ResRun q;
+  q.n = r.n; q.offset = r.offset; q.n_total = r.n_total; q.a = r.a; q.lab = r.lab;
+  q.u = r.u ? r.u + (size_t)(t0 - r.u_t0) * r.u_ld : nullptr;
+  q.u_ld = r.u_ld; q.seed = r.seed; q.ge_iter = r.ge_iter; q.t0 = t0; q.n_periods = n_periods;
+  q.sow = r.sow; q.hist_A = r.hist_A; q.hist_M = r.hist_M; q.flags = flags;
+  return q;
+}
+
 }  // namespace aiy
 
 using namespace aiy;
@@ -271,48 +301,37 @@ extern "C" int32_t aiy_sim_periods(aiy_handle* h, const aiy_panel_model* model, 
   PanelDev P;
   int32_t rc = panel_dev(h, model, P);
   if (rc) return rc;
-  if (n_local < 0 || n_total < 1 || agent_offset < 0) return fail(h, AIY_ERR_ARG, "bad agent counts");
-  if (n_local > 0 && (!a || !lab)) return fail(h, AIY_ERR_ARG, "null agent arrays");
+  PanelRun r;
+  r.n = n_local; r.offset = agent_offset; r.n_total = n_total; r.a = a; r.lab = lab;
+  r.u = u; r.u_ld = u_ld; r.u_t0 = t0; r.emp = emp; r.emp_ld = emp_ld;
+  r.seed = seed; r.ge_iter = ge_iter; r.sow = sow; r.hist_A = hist_A; r.hist_M = hist_M; r.finish = h->comm ? 0 : 1;
+  if (n_total < 1) return fail(h, AIY_ERR_ARG, "bad agent counts");
+  rc = check_run(h, P, r);
+  if (rc) return rc;
   if (u && u_ld < n_local) return fail(h, AIY_ERR_ARG, "u_ld < n_local");
   if (emp && emp_ld < n_local) return fail(h, AIY_ERR_ARG, "emp_ld < n_local");
-  if (emp && !P.unemployed) return fail(h, AIY_ERR_ARG, "employment states need tables with the unemployed cells");
   if (t0 < 0 || n_periods < 0 || t0 + (int64_t)n_periods > P.act_T)
     return fail(h, AIY_ERR_ARG, "bad period range [%d, %lld) for act_T=%d", t0, (long long)t0 + n_periods, P.act_T);
-  if (ge_iter >= (1u << 12)) return fail(h, AIY_ERR_ARG, "ge_iter too large for the Philox counter");
   if (!h->comm && n_local != n_total) return fail(h, AIY_ERR_ARG, "n_local != n_total without a communicator");
   if (n_periods == 0) return AIY_OK;
-  AIY_HIP(h, hipSetDevice(h->device));
-  rc = ensure_panel_scratch(h);
-  if (rc) return rc;
   hipStream_t st = as_stream(stream);
-  rc = use_stream(h, st);
+  rc = bind_run(h, r, t0, st);
   if (rc) return rc;
   const int nb = sim_blocks(n_local);
-  PanelRun r;
-  r.n = n_local; r.offset = agent_offset; r.n_total = n_total; r.a = a; r.lab = lab; r.u = u; r.u_ld = u_ld;
-  r.u_t0 = t0; r.emp = emp; r.emp_ld = emp_ld; r.seed = seed; r.ge_iter = ge_iter; r.sow = sow;
-  r.partials = h->partials.as<double>(); r.ticket = h->ticket.as<unsigned>();
-  r.hist_A = hist_A; r.hist_M = hist_M; r.finish = h->comm ? 0 : 1;
   const aiy_market mk = *mkt;
 
-  // the persistent kernel simulates the employed sub-states only (Krusell-Smith mode runs
-  // the per-period kernel)
-  const bool res_ok = h->use_resident && !emp && n_local >= kResMinAgents && resident_supported(P) &&
-                      resident_aligned(a, lab);
-  // (its Philox pairs (2k, 2k + 1) must not straddle shards: an even agent_offset)
-  if (h->comm && res_ok && (agent_offset & 1) == 0) {
+  const bool res_ok = resident_eligible(h, P, n_local, a, lab, emp, agent_offset, h->comm != nullptr);
+  if (h->comm && res_ok) {
     // sharded: per period ONE launch of the tuned resident kernel (its streaming form for shards
     // beyond LDS, e.g. 12.5M agents per rank at configs[3] on 8 GPUs) leaving the shard's sum in
     // sow[6], the RCCL all-reduce of that double, and the price kernel (mill, AS:1867-1894);
     // the next period's labour draws ride at the end of each launch
     // (period t's launch forms period t - 1's prices from the all-reduced sum itself; the price
     // kernel runs once, after the last all-reduce)
-    hipLaunchKernelGGL(set_period_kernel, dim3(1), dim3(64), 0, st, sow, (int)t0);
     for (int p = 0; p < n_periods; ++p) {
       const int fl = kResSharded | (p == 0 ? kResDraw0 : kResPrices | kResKeepTmo) |
                      (p + 1 < n_periods ? kResDrawNext : 0);
-      rc = launch_resident(h, P, mk, n_local, a, lab, u ? u + (size_t)p * u_ld : nullptr, u_ld, seed, ge_iter, t0 + p,
-                           1, sow, hist_A, hist_M, st, agent_offset, fl, n_total);
+      rc = launch_resident(h, P, mk, resident_run(r, t0 + p, 1, fl), st);
       if (rc) return rc;
       const ncclResult_t e = ncclAllReduce(sow + 6, sow + 6, 1, ncclDouble, ncclSum, h->comm, st);
       if (e != ncclSuccess) return fail(h, AIY_ERR_COMM, "ncclAllReduce: %s", ncclGetErrorString(e));
@@ -322,15 +341,13 @@ extern "C" int32_t aiy_sim_periods(aiy_handle* h, const aiy_panel_model* model, 
     AIY_CHECK_LAUNCH(h);
     return resident_status(h, st, false);
   }
-  if (!h->comm && res_ok) {
+  if (res_ok) {
     // one persistent launch for the whole block of periods (panel_resident.hip)
-    hipLaunchKernelGGL(set_period_kernel, dim3(1), dim3(64), 0, st, sow, (int)t0);
-    rc = launch_resident(h, P, mk, n_local, a, lab, u, u_ld, seed, ge_iter, t0, n_periods, sow, hist_A, hist_M, st);
+    rc = launch_resident(h, P, mk, resident_run(r, t0, n_periods, kResDraw0), st);
     if (rc) return rc;
     AIY_CHECK_LAUNCH(h);
     return resident_status(h, st);
   }
-  hipLaunchKernelGGL(set_period_kernel, dim3(1), dim3(64), 0, st, sow, (int)t0);
   int done = 0;
   if (h->use_graphs && !h->comm && n_periods >= 2 * kGraphPeriods) {
     // Capture kGraphPeriods identical periods on the handle's capture stream, replay.
@@ -373,35 +390,26 @@ extern "C" int32_t aiy_sim_period_local(aiy_handle* h, const aiy_panel_model* mo
   PanelDev P;
   int32_t rc = panel_dev(h, model, P);
   if (rc) return rc;
-  if (n_local < 0 || agent_offset < 0) return fail(h, AIY_ERR_ARG, "bad agent counts");
-  if (n_local > 0 && (!a || !lab)) return fail(h, AIY_ERR_ARG, "null agent arrays");
+  PanelRun r;   // (no history, finish = 0: the step publishes the shard's sum only)
+  r.n = n_local; r.offset = agent_offset; r.n_total = n_local; r.a = a; r.lab = lab;
+  r.u = u; r.u_ld = n_local; r.u_t0 = t; r.emp = emp; r.emp_ld = n_local;
+  r.seed = seed; r.ge_iter = ge_iter; r.sow = sow;
+  rc = check_run(h, P, r);
+  if (rc) return rc;
   if (t < 0 || t >= P.act_T) return fail(h, AIY_ERR_ARG, "period t=%d outside [0, act_T=%d)", t, P.act_T);
-  if (ge_iter >= (1u << 12)) return fail(h, AIY_ERR_ARG, "ge_iter too large for the Philox counter");
-  if (emp && !P.unemployed) return fail(h, AIY_ERR_ARG, "employment states need tables with the unemployed cells");
-  AIY_HIP(h, hipSetDevice(h->device));
-  rc = ensure_panel_scratch(h);
-  if (rc) return rc;
   hipStream_t st = as_stream(stream);
-  rc = use_stream(h, st);
+  rc = bind_run(h, r, t, st);
   if (rc) return rc;
-  PanelRun r;
-  r.n = n_local; r.offset = agent_offset; r.n_total = n_local; r.a = a; r.lab = lab; r.u = u; r.u_ld = n_local;
-  r.u_t0 = t; r.emp = emp; r.emp_ld = n_local; r.seed = seed; r.ge_iter = ge_iter; r.sow = sow; r.partials = h->partials.as<double>(); r.ticket = h->ticket.as<unsigned>();
-  r.hist_A = nullptr; r.hist_M = nullptr; r.finish = 0;
-  hipLaunchKernelGGL(set_period_kernel, dim3(1), dim3(64), 0, st, sow, (int)t);
-  if (h->use_resident && !emp && n_local >= kResMinAgents && resident_supported(P) && resident_aligned(a, lab) &&
-      (agent_offset & 1) == 0) {
+  const aiy_market no_prices{};   // this step forms none (aiy_sim_period_prices does)
+  if (resident_eligible(h, P, n_local, a, lab, emp, agent_offset, true)) {
     // the tuned resident kernel, one period (its labour draws first), the shard's sum in sow[6]
-    const aiy_market unused{};
-    rc = launch_resident(h, P, unused, n_local, a, lab, u, n_local, seed, ge_iter, t, 1, sow, nullptr, nullptr, st,
-                         agent_offset, kResSharded | kResDraw0);
+    rc = launch_resident(h, P, no_prices, resident_run(r, t, 1, kResSharded | kResDraw0), st);
     if (rc) return rc;
     AIY_CHECK_LAUNCH(h);
     return resident_status(h, st, false);
   }
   if (n_local > 0) {
-    const aiy_market unused{};
-    hipLaunchKernelGGL(sim_period_kernel, dim3(sim_blocks(n_local)), dim3(kSimBlock), 0, st, P, r, unused);
+    hipLaunchKernelGGL(sim_period_kernel, dim3(sim_blocks(n_local)), dim3(kSimBlock), 0, st, P, r, no_prices);
   } else {
     hipLaunchKernelGGL(zero_sum_kernel, dim3(1), dim3(64), 0, st, sow);
   }
@@ -443,119 +451,25 @@ extern "C" int32_t aiy_sim_kernel_time(aiy_handle* h, const aiy_panel_model* mod
   int32_t rc = panel_dev(h, model, P);
   if (rc) return rc;
   if (n_launch > P.act_T) return fail(h, AIY_ERR_ARG, "n_launch=%d > act_T=%d", n_launch, P.act_T);
-  AIY_HIP(h, hipSetDevice(h->device));
-  rc = ensure_panel_scratch(h);
+  PanelRun r;   // (Philox shocks, everyone employed, no history)
+  r.n = n_local; r.n_total = n_local; r.a = a; r.lab = lab; r.seed = seed; r.ge_iter = ge_iter; r.sow = sow; r.finish = 1;
+  rc = check_run(h, P, r);
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
-  rc = use_stream(h, st);
+  rc = bind_run(h, r, 0, st);
   if (rc) return rc;
-  PanelRun r;
-  r.n = n_local; r.offset = 0; r.n_total = n_local; r.a = a; r.lab = lab; r.u = nullptr; r.u_ld = 0; r.u_t0 = 0;
-  r.emp = nullptr; r.emp_ld = 0; r.seed = seed; r.ge_iter = ge_iter; r.sow = sow; r.partials = h->partials.as<double>(); r.ticket = h->ticket.as<unsigned>();
-  r.hist_A = nullptr; r.hist_M = nullptr; r.finish = 1;
-  const int nb = sim_blocks(n_local);
-  hipLaunchKernelGGL(set_period_kernel, dim3(1), dim3(64), 0, st, sow, 0);
   AIY_CHECK_LAUNCH(h);
-  if (h->use_resident && n_local >= kResMinAgents && resident_supported(P) &&
-      resident_aligned(a, lab)) {
+  if (resident_eligible(h, P, n_local, a, lab, nullptr, 0, false)) {
     // one persistent launch of n_launch periods
-    rc = time_launches(h, st, 1,
-                       [&] {
-                         (void)launch_resident(h, P, *mkt, n_local, a, lab, nullptr, 0, seed, ge_iter, 0, n_launch, sow,
-                                               nullptr, nullptr, st);
-                       },
+    int32_t lrc = AIY_OK;
+    rc = time_launches(h, st, 1, [&] { lrc = launch_resident(h, P, *mkt, resident_run(r, 0, n_launch, kResDraw0), st); },
                        ms_out);
+    if (lrc) return lrc;
     if (rc) return rc;
     return resident_status(h, st);
   }
+  const int nb = sim_blocks(n_local);
   return time_launches(h, st, n_launch,
                        [&] { hipLaunchKernelGGL(sim_period_kernel, dim3(nb), dim3(kSimBlock), 0, st, P, r, *mkt); },
                        ms_out);
-}
-
-extern "C" int32_t aiy_set_option(aiy_handle* h, int32_t option, int64_t value) {
-  if (!h) return AIY_ERR_ARG;
-  switch (option) {
-    case AIY_OPT_USE_GRAPHS: h->use_graphs = value != 0; return AIY_OK;
-    case AIY_OPT_RESIDENT:
-      h->use_resident = value != 0;
-      return AIY_OK;
-    case AIY_OPT_RESIDENT_SHAPE:
-      if (value < 0 || value > 2) return fail(h, AIY_ERR_ARG, "AIY_OPT_RESIDENT_SHAPE must be 0, 1 or 2");
-      h->res_shape = (int)value;
-      return AIY_OK;
-    case AIY_OPT_HIST_FUSED: h->hist_fused = value != 0; return AIY_OK;
-    case AIY_OPT_RESIDENT_STREAM: h->res_stream = value != 0; return AIY_OK;
-    case AIY_OPT_HIST_RESIDENT: h->hist_resident = value != 0; return AIY_OK;
-    case AIY_OPT_HIST_ACCEL:
-      if (value < 0 || value > (1 << 20)) return fail(h, AIY_ERR_ARG, "AIY_OPT_HIST_ACCEL must be >= 0");
-      h->hist_accel = (int)value;
-      return AIY_OK;
-    case AIY_OPT_HIST_KRYLOV: h->hist_krylov = value != 0; return AIY_OK;
-    case AIY_OPT_HIST_PULL: h->hist_pull = value != 0; return AIY_OK;
-    case AIY_OPT_HIST_IID: h->hist_iid = value != 0; return AIY_OK;
-    case AIY_OPT_RESIDENT_SHAPE_STREAM:
-      if (value < -1 || value > 2) return fail(h, AIY_ERR_ARG, "AIY_OPT_RESIDENT_SHAPE_STREAM must be -1, 0, 1 or 2");
-      h->res_shape_stream = (int)value;
-      return AIY_OK;
-    case AIY_OPT_GE_LOOSE_HIST:
-      if (value < 6 || value > 14) return fail(h, AIY_ERR_ARG, "AIY_OPT_GE_LOOSE_HIST must be in [6, 14]");
-      h->ge_loose_hist = (int)value;
-      return AIY_OK;
-    case AIY_OPT_GE_RESIDENT: h->ge_resident = value != 0; return AIY_OK;
-    case AIY_OPT_GE_LOGSEC:
-      if (value < 0 || value > 2) return fail(h, AIY_ERR_ARG, "AIY_OPT_GE_LOGSEC must be 0, 1 or 2");
-      h->ge_logsec = (int)value;
-      return AIY_OK;
-    case AIY_OPT_GE_EXTRAP_PERIOD:
-      if (value < 4 || value > 1024) return fail(h, AIY_ERR_ARG, "AIY_OPT_GE_EXTRAP_PERIOD must be in [4, 1024]");
-      h->ge_extrap_period = (int)value;
-      return AIY_OK;
-    case AIY_OPT_GE_ANDERSON:
-      if (value != 0 && (value < 5 || value > 1024))
-        return fail(h, AIY_ERR_ARG, "AIY_OPT_GE_ANDERSON must be 0 or in [5, 1024]");
-      h->ge_anderson = (int)value;
-      return AIY_OK;
-    case AIY_OPT_GE_REBALANCE:
-      if (value < 0 || value > 100) return fail(h, AIY_ERR_ARG, "AIY_OPT_GE_REBALANCE must be in [0, 100]");
-      h->ge_rebalance = (int)value;
-      return AIY_OK;
-    case AIY_OPT_CU_LIMIT:
-      if (value < 0 || value > 65536) return fail(h, AIY_ERR_ARG, "AIY_OPT_CU_LIMIT must be in [0, 65536]");
-      h->cu_limit = (int)value;
-      return AIY_OK;
-    case AIY_OPT_HIST_CLUSTER:
-      if (value < 0 || value > 128) return fail(h, AIY_ERR_ARG, "AIY_OPT_HIST_CLUSTER must be in [0, 128]");
-      h->hist_cluster_cap = (int)value;
-      return AIY_OK;
-    default: return fail(h, AIY_ERR_ARG, "unknown option %d", option);
-  }
-}
-
-// Current value of a handle option (the values aiy_set_option takes), so callers can save
-// and restore what they change.
-extern "C" int32_t aiy_get_option(aiy_handle* h, int32_t option, int64_t* value) {
-  if (!h || !value) return AIY_ERR_ARG;
-  switch (option) {
-    case AIY_OPT_USE_GRAPHS: *value = h->use_graphs; return AIY_OK;
-    case AIY_OPT_RESIDENT: *value = h->use_resident; return AIY_OK;
-    case AIY_OPT_RESIDENT_SHAPE: *value = h->res_shape; return AIY_OK;
-    case AIY_OPT_HIST_FUSED: *value = h->hist_fused; return AIY_OK;
-    case AIY_OPT_RESIDENT_STREAM: *value = h->res_stream; return AIY_OK;
-    case AIY_OPT_HIST_RESIDENT: *value = h->hist_resident; return AIY_OK;
-    case AIY_OPT_HIST_ACCEL: *value = h->hist_accel; return AIY_OK;
-    case AIY_OPT_HIST_KRYLOV: *value = h->hist_krylov; return AIY_OK;
-    case AIY_OPT_HIST_PULL: *value = h->hist_pull; return AIY_OK;
-    case AIY_OPT_HIST_IID: *value = h->hist_iid; return AIY_OK;
-    case AIY_OPT_RESIDENT_SHAPE_STREAM: *value = h->res_shape_stream; return AIY_OK;
-    case AIY_OPT_GE_LOOSE_HIST: *value = h->ge_loose_hist; return AIY_OK;
-    case AIY_OPT_GE_RESIDENT: *value = h->ge_resident; return AIY_OK;
-    case AIY_OPT_GE_LOGSEC: *value = h->ge_logsec; return AIY_OK;
-    case AIY_OPT_GE_EXTRAP_PERIOD: *value = h->ge_extrap_period; return AIY_OK;
-    case AIY_OPT_GE_ANDERSON: *value = h->ge_anderson; return AIY_OK;
-    case AIY_OPT_GE_REBALANCE: *value = h->ge_rebalance; return AIY_OK;
-    case AIY_OPT_CU_LIMIT: *value = h->cu_limit; return AIY_OK;
-    case AIY_OPT_HIST_CLUSTER: *value = h->hist_cluster_cap; return AIY_OK;
-    default: return fail(h, AIY_ERR_ARG, "unknown option %d", option);
-  }
 }

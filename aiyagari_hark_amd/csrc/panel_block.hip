@@ -61,10 +61,8 @@ __global__ __launch_bounds__(kBlkMaxThreads) void panel_block_kernel(BatchDev B,
   const int nthr = blockDim.x;
   const int n = (int)r.n;
   uint8_t* s_lab = reinterpret_cast<uint8_t*>(s_a + n);
-  const int n_M = B.n_M, n_lab = B.n_lab;
   const PanelTab T = panel_tab(B.tables + (size_t)cal * B.g.bytes, B.g);
-  const int n_J = B.g.n_J;
-  const double* Mg = B.M_grid + (size_t)cal * n_M;
+  const double* Mg = B.M_grid + (size_t)cal * B.n_M;
   const int* hist = B.mrkv_hist + (size_t)cal * B.act_T;
   const aiy_market mk = r.mk[cal];
   const unsigned long long seed = r.seeds[cal];
@@ -72,13 +70,12 @@ __global__ __launch_bounds__(kBlkMaxThreads) void panel_block_kernel(BatchDev B,
   double* ga = r.a + (size_t)cal * n;
   uint8_t* glab = r.lab + (size_t)cal * n;
 
-  __shared__ double s_cdf[kLdsLab * kLdsLab];
-  __shared__ double s_lvl[kLdsLab];
-  __shared__ CellHdr s_hdr[2 * kLdsLab];
+  __shared__ PanelLds lds;
   __shared__ double s_red[kBlkMaxThreads / kWave];
   __shared__ double s_price[4];   // Mnow, Rnow, Wnow, Mrkv
-  for (int q = tid; q < n_lab * n_lab; q += nthr) s_cdf[q] = B.lab_cdf[(size_t)cal * n_lab * n_lab + q];
-  for (int q = tid; q < n_lab; q += nthr) s_lvl[q] = B.lab_level[(size_t)cal * n_lab + q];
+  Period pd;
+  pd.n_lab = B.n_lab; pd.n_J = B.g.n_J; pd.blend = B.n_M > 1; pd.s = &lds;
+  stage_labour(&lds, B.lab_cdf + (size_t)cal * B.n_lab * B.n_lab, B.lab_level + (size_t)cal * B.n_lab, B.n_lab);
   for (int q = tid; q < n; q += nthr) {
     s_a[q] = ga[q];
     s_lab[q] = glab[q];
@@ -95,15 +92,9 @@ __global__ __launch_bounds__(kBlkMaxThreads) void panel_block_kernel(BatchDev B,
   Prices last{};
   for (int p = 0; p < r.n_periods; ++p) {
     const int t = r.t0 + p;
-    const double Mnow = s_price[0], Rnow = s_price[1], Wnow = s_price[2];
-    const int Mrkv = (int)s_price[3];
-    int jc;
-    double alpha;
-    m_bracket(Mg, n_M, Mnow, jc, alpha);
-    for (int q = tid; q < n_lab; q += nthr) {
-      s_hdr[q] = cell_header(T, panel_cell(q, 1, Mrkv, n_lab, n_J, jc));
-      if (r.emp) s_hdr[n_lab + q] = cell_header(T, panel_cell(q, 0, Mrkv, n_lab, n_J, jc));
-    }
+    pd.R = s_price[1]; pd.W = s_price[2]; pd.Mrkv = (int)s_price[3];
+    m_bracket(Mg, B.n_M, s_price[0], pd.jc, pd.alpha);
+    stage_headers(T, pd, r.emp != nullptr);
     __syncthreads();
     const unsigned ctr0 = (r.ge_iter << 20) | (unsigned)t;
     const double* u = r.u ? r.u + ((size_t)cal * r.n_periods + p) * n : nullptr;
@@ -111,53 +102,38 @@ __global__ __launch_bounds__(kBlkMaxThreads) void panel_block_kernel(BatchDev B,
     double local = 0.0;
     for (int g = tid; g < n_groups; g += nthr) {
       const int i0 = g * A;
-      double m[A];
-      int ln[A], ev[A];
+      double ap[A], uu[A], an[A];
+      int lp[A], ln[A], ev[A];
 #pragma unroll
       for (int kk = 0; kk < A / 2; ++kk) {
         const int ia = i0 + 2 * kk;
-        double uu[2];
         if (u) {
-          uu[0] = ia < n ? u[ia] : 0.0;
-          uu[1] = ia + 1 < n ? u[ia + 1] : 0.0;
+          uu[2 * kk] = ia < n ? u[ia] : 0.0;
+          uu[2 * kk + 1] = ia + 1 < n ? u[ia + 1] : 0.0;
         } else {
-          philox_uniform2(ctr0, (uint64_t)(ia >> 1), seed, 0u, uu[0], uu[1]);
-        }
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int k = 2 * kk + e;
-          const int i = ia + e < n ? ia + e : n - 1;
-          const int l0 = s_lab[i];
-          int l = 0;
-          for (int q = 0; q < n_lab; ++q) l += (s_cdf[l0 * n_lab + q] <= uu[e]) ? 1 : 0;  // searchsorted 'right'
-          ln[k] = l;
-          ev[k] = em ? (int)em[i] : 1;                                                    // EmpNow (AS:1222-1240)
-          m[k] = Rnow * s_a[i] + Wnow * (s_lvl[l] * (double)ev[k]);                      // AS:1283
+          philox_uniform2(ctr0, (uint64_t)(ia >> 1), seed, 0u, uu[2 * kk], uu[2 * kk + 1]);
         }
       }
-      int cell[A], hx[A];
 #pragma unroll
       for (int k = 0; k < A; ++k) {
-        cell[k] = panel_cell(ln[k], ev[k], Mrkv, n_lab, n_J, jc);                      // AS:1326-1356
-        hx[k] = panel_hdr(ln[k], ev[k], n_lab);
+        const int i = i0 + k < n ? i0 + k : n - 1;   // tail lanes: dummy work on the last agent
+        lp[k] = s_lab[i];
+        ap[k] = s_a[i];
+        ev[k] = em ? (int)em[i] : 1;                 // EmpNow (AS:1222-1240)
       }
-      double c[A];
-      tab_policy<A>(T, cell, s_hdr, hx, m, alpha, n_M > 1, c);                                  // AS:1326-1408
+      agent_step<A>(T, pd, lp, uu, ap, ev, ln, an);
 #pragma unroll
       for (int k = 0; k < A; ++k) {
         const int i = i0 + k;
         if (i < n) {
-          const double an = m[k] - c[k];                                                 // AS:1415
-          s_a[i] = an;
+          s_a[i] = an[k];
           s_lab[i] = (uint8_t)ln[k];
-          local += an;
+          local += an[k];
         }
       }
     }
     // workgroup sum of a (fixed order), then calc_R_and_W by lane 0
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, kWave);
-    if ((tid & (kWave - 1)) == 0) s_red[tid / kWave] = local;
+    wave_partials(local, s_red);
     __syncthreads();
     if (tid == 0) {
       double tot = 0.0;
@@ -177,15 +153,7 @@ __global__ __launch_bounds__(kBlkMaxThreads) void panel_block_kernel(BatchDev B,
     ga[q] = s_a[q];
     glab[q] = s_lab[q];
   }
-  if (tid == 0) {
-    store_f64_agent(&sow[0], last.Mnow);
-    store_f64_agent(&sow[1], last.Aprev);
-    store_f64_agent(&sow[2], (double)last.Mrkv);
-    store_f64_agent(&sow[3], last.Rnow);
-    store_f64_agent(&sow[4], last.Wnow);
-    store_f64_agent(&sow[5], 0.0);
-    store_f64_agent(&sow[7], (double)(r.t0 + r.n_periods));
-  }
+  if (tid == 0) store_sow(sow, last, r.t0 + r.n_periods);
 }
 
 }  // namespace aiy
@@ -244,14 +212,13 @@ extern "C" int32_t aiy_sim_block_periods(aiy_handle* h, const aiy_panel_batch* m
   const long long groups = (n_agents + A - 1) / A;
   int thr = (int)std::min<long long>(kBlkMaxThreads, std::max<long long>(kWave, (groups + kWave - 1) / kWave * kWave));
   const size_t lds = (size_t)n_agents * (sizeof(double) + 1);
-  static bool attr_set = false;   // LDS beyond the 64 KiB default (gfx950: 160 KiB per CU)
-  if (!attr_set) {
+  if (!h->blk_attr_set) {   // LDS beyond the 64 KiB default (gfx950: 160 KiB per CU), on this handle's device
     const int max_lds = kBlkMaxAgents * (int)(sizeof(double) + 1);
     AIY_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(panel_block_kernel<2>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     AIY_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(panel_block_kernel<4>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    attr_set = true;
+    h->blk_attr_set = true;
   }
   dim3 grid(M.n_cal), block(thr);
   if (A == 2) hipLaunchKernelGGL(panel_block_kernel<2>, grid, block, lds, st, B, r);

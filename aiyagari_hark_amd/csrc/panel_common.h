@@ -1,5 +1,6 @@
 // Device helpers shared by the panel kernels (panel.hip, panel_block.hip,
-// panel_resident.hip) and the merged policy tables they read (panel_tab.hip).
+// panel_resident.hip), the hooks (hooks.hip) and the merged policy tables they read
+// (panel_tab.hip): the table lookup, the agent step, the resident launch plan.
 #pragma once
 
 #include "common.h"
@@ -345,6 +346,93 @@ constexpr int kLdsLab = 16;   // labour states (the KS form has S = 4 n_lab <= 6
 constexpr int kPairs = 2;     // agent pairs per lane per pass
 constexpr int kAgents = 2 * kPairs;
 
+// ---------------------------------------------------------------------------------
+// The agent step of the block kernel (panel_block.hip); the hooks (hooks.hip) take its two
+// formulas.  The resident kernel (panel_resident.hip) shares the labour draw only: its
+// instantiations sit on the register limit and keep their own m and price staging.  The
+// per-period kernel (panel.hip) keeps its own text of the step too: through agent_step it ran
+// 26.2 against 25.6 us per period at 1e6 agents (same registers, another schedule).  The
+// library is built with -ffp-contract=off; the operand order here is the bits.
+// ---------------------------------------------------------------------------------
+// get_shocks (AS:1253-1254): np.random.choice's inverse CDF on the row of the previous state.
+__device__ __forceinline__ int draw_labour(const double* s_cdf, int n_lab, int l0, double u) {
+  int l = 0;
+  for (int q = 0; q < n_lab; ++q) l += (s_cdf[l0 * n_lab + q] <= u) ? 1 : 0;   // searchsorted(cdf, u, 'right')
+  return l;
+}
+
+// get_states (AS:1283): m = Rnow a_prev + Wnow LSStates[l] Emp
+__device__ __forceinline__ double cash_on_hand(double R, double W, double a, double lvl, double emp) {
+  return R * a + W * (lvl * emp);
+}
+
+// The labour chain (inverse CDF rows, levels) and the period's cell headers in LDS: the
+// per-agent dependent chain then has no global hop before the policy lookup.
+struct PanelLds {
+  double cdf[kLdsLab * kLdsLab];
+  double lvl[kLdsLab];
+  CellHdr hdr[2 * kLdsLab];   // employed [n_lab], then unemployed [n_lab]
+};
+
+// One period's scalars and LDS pointers.
+struct Period {
+  double R, W, alpha;   // alpha: blend weight of the M bracket (m_bracket)
+  int Mrkv, jc, n_lab, n_J;
+  bool blend;           // n_M > 1
+  PanelLds* s;
+};
+
+// Workgroup-strided; the caller barriers.
+__device__ __forceinline__ void stage_labour(PanelLds* s, const double* cdf, const double* lvl, int n_lab) {
+  for (int q = threadIdx.x; q < n_lab * n_lab; q += blockDim.x) s->cdf[q] = cdf[q];
+  for (int q = threadIdx.x; q < n_lab; q += blockDim.x) s->lvl[q] = lvl[q];
+}
+__device__ __forceinline__ void stage_headers(const PanelTab& T, const Period& p, bool unemployed) {
+  for (int q = threadIdx.x; q < p.n_lab; q += blockDim.x) {
+    p.s->hdr[q] = cell_header(T, panel_cell(q, 1, p.Mrkv, p.n_lab, p.n_J, p.jc));
+    if (unemployed) p.s->hdr[p.n_lab + q] = cell_header(T, panel_cell(q, 0, p.Mrkv, p.n_lab, p.n_J, p.jc));
+  }
+}
+
+// A lane's NA agents from (previous labour state, uniform, asset, employment) to (new labour
+// state, a'), their dependent chains in lock step (tab_policy).
+template <int NA>
+__device__ __forceinline__ void agent_step(const PanelTab& T, const Period& p, const int (&lp)[NA],
+                                           const double (&u)[NA], const double (&a)[NA], const int (&ev)[NA],
+                                           int (&ln)[NA], double (&an)[NA]) {
+  double m[NA], c[NA];
+  int cell[NA], hx[NA];
+#pragma unroll
+  for (int k = 0; k < NA; ++k) {
+    ln[k] = draw_labour(p.s->cdf, p.n_lab, lp[k], u[k]);
+    m[k] = cash_on_hand(p.R, p.W, a[k], p.s->lvl[ln[k]], (double)ev[k]);                   // AS:1283
+    cell[k] = panel_cell(ln[k], ev[k], p.Mrkv, p.n_lab, p.n_J, p.jc);                       // AS:1326-1356
+    hx[k] = panel_hdr(ln[k], ev[k], p.n_lab);
+  }
+  tab_policy<NA>(T, cell, p.s->hdr, hx, m, p.alpha, p.blend, c);                            // AS:1326-1408
+#pragma unroll
+  for (int k = 0; k < NA; ++k) an[k] = m[k] - c[k];                                         // AS:1415
+}
+
+// The next sow_state: the prices of the period just milled and the index of the next period.
+__device__ __forceinline__ void store_sow(double* sow, const Prices& p, int t_next) {
+  store_f64_agent(&sow[0], p.Mnow);
+  store_f64_agent(&sow[1], p.Aprev);
+  store_f64_agent(&sow[2], (double)p.Mrkv);
+  store_f64_agent(&sow[3], p.Rnow);
+  store_f64_agent(&sow[4], p.Wnow);
+  store_f64_agent(&sow[5], 0.0);  // Urate is recorded by the caller (it draws the employment)
+  store_f64_agent(&sow[7], (double)t_next);
+}
+
+// Wave sums of v by __shfl_down; lane 0 of every wave leaves its wave's in red[wave].  The
+// caller barriers and combines the partials in its own fixed order.
+__device__ __forceinline__ void wave_partials(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
+  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
+}
+
 // Host: check the model of one calibration and fill its device view.
 int32_t panel_dev(aiy_handle* h, const aiy_panel_model* model, PanelDev& P);
 
@@ -359,10 +447,26 @@ int32_t panel_dev(aiy_handle* h, const aiy_panel_model* model, PanelDev& P);
 // word is not re-zeroed (an earlier launch of the same call zeroed it; the host reads it once
 // at the end).
 constexpr int kResSharded = 1, kResDraw0 = 2, kResDrawNext = 4, kResPrices = 8, kResKeepTmo = 16;
-int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, long long n, double* a, uint8_t* lab,
-                        const double* u, long long u_ld, unsigned long long seed, unsigned ge_iter, int t0,
-                        int n_periods, double* sow, double* hist_A, double* hist_M, hipStream_t st,
-                        long long offset = 0, int flags = kResDraw0, long long n_total = 0);
+// One resident launch: the caller names what it sets, launch_resident adds the geometry and the
+// exchange words (chunk, gran, tmo, ep0).
+struct ResRun {
+  long long n = 0, offset = 0;   // local agents; global index of local agent 0 (Philox)
+  long long chunk = 0;           // agents per workgroup (even)
+  double* a = nullptr; uint8_t* lab = nullptr;
+  const double* u = nullptr;     // host uniforms [n_periods][u_ld] from period t0, or nullptr
+  long long u_ld = 0;
+  unsigned long long seed = 0; unsigned ge_iter = 0;
+  int t0 = 0, n_periods = 0;
+  double* sow = nullptr;
+  unsigned long long* gran = nullptr; // [2 parity][nb][2] tagged halves of the workgroup partials, zeroed
+  unsigned* tmo = nullptr;            // timeout word, zeroed
+  double* hist_A = nullptr; double* hist_M = nullptr;
+  unsigned ep0 = 0;              // granule tags of period p carry ep0 + p + 1 (unique across launches)
+  long long n_total = 0;         // agents over all ranks (the mill's mean, kResPrices)
+  int flags = kResDraw0;         // kResSharded | kResDraw0 | kResDrawNext | kResPrices | kResKeepTmo
+};
+// mk: the market of the launch's own price updates (unused by a launch that forms none).
+int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, ResRun r, hipStream_t st);
 int32_t resident_status(aiy_handle* h, hipStream_t st, bool timed = true);
 bool resident_supported(const PanelDev& P);
 // the persistent kernel moves agent pairs as 16-byte asset / 2-byte labour accesses

@@ -43,41 +43,21 @@ constexpr unsigned long long kResTimeoutTicks = 400000000ull;  // 4 s of the 100
 constexpr size_t kResGranBytes = sizeof(unsigned long long) * 2 * 2 * kResMaxBlocks;
 constexpr size_t kResSyncBytes = kResGranBytes + 16;          // + timeout word, padded to 16 B
 
-struct ResRun {
-  long long n, offset;       // local agents; global index of local agent 0 (Philox)
-  long long chunk;           // agents per workgroup (even)
-  double* a;
-  uint8_t* lab;
-  const double* u;           // host uniforms [n_periods][u_ld] from period t0, or nullptr
-  long long u_ld;
-  unsigned long long seed;
-  unsigned ge_iter;
-  int t0, n_periods;
-  double* sow;
-  unsigned long long* gran; // [2 parity][nb][2] tagged halves of the workgroup partials, zeroed
-  unsigned* tmo;            // timeout word, zeroed
-  double* hist_A;
-  double* hist_M;
-  unsigned ep0;             // granule tags of period p carry ep0 + p + 1 (unique across launches)
-  long long n_total;        // agents over all ranks (the mill's mean, kResPrices)
-  int flags;                // kResSharded | kResDraw0 | kResDrawNext
-};
-
-__device__ __forceinline__ int draw_labour(const double* s_cdf, int n_lab, int l0, double u) {
-  int l = 0;
-  for (int q = 0; q < n_lab; ++q) l += (s_cdf[l0 * n_lab + q] <= u) ? 1 : 0;   // searchsorted(cdf, u, 'right')
-  return l;
-}
-
 // Labour states of period t for the slice (in place: lab(t-1) -> lab(t)).  Each thread
 // draws kDrawGroup agent pairs at once: their Philox chains are independent, so they
 // overlap instead of running back to back (the draw sits on the critical path of the
 // workgroup that publishes last).
 // Thread `vt` of `nvt` drawing threads takes agent pairs vt, vt + nvt, ..., G at a time.
 constexpr int kDrawGroup = 4;
+struct Slice {   // a workgroup's agents: their labour states, the local index of the first, their number
+  uint8_t* L; long long start; int cnt;
+};
 template <int G>
-__device__ __forceinline__ void draw_slice(const ResRun& r, long long offset, uint8_t* L, long long start, int cnt, int t,
+__device__ __forceinline__ void draw_slice(const ResRun& r, long long offset, const Slice& sl, int t,
                                            const double* s_cdf, int n_lab, int vt, int nvt) {
+  uint8_t* const L = sl.L;
+  const long long start = sl.start;
+  const int cnt = sl.cnt;
   const unsigned ctr0 = (r.ge_iter << 20) | (unsigned)t;
   const double* u = r.u ? r.u + (size_t)(t - r.t0) * r.u_ld + start : nullptr;
   const int nthr = nvt;
@@ -205,7 +185,7 @@ __global__ __launch_bounds__(TH) void sim_resident_kernel(PanelDev P, ResRun r, 
     }
   }
   __syncthreads();
-  if (flags & kResDraw0) draw_slice<kDrawGroup>(r, offset, L, start, cnt, r.t0, s_cdf, n_lab, tid, TH);
+  if (flags & kResDraw0) draw_slice<kDrawGroup>(r, offset, Slice{L, start, cnt}, r.t0, s_cdf, n_lab, tid, TH);
   __syncthreads();   // period t0's labour draws complete
   const bool sharded = SHARD && (flags & kResSharded) != 0;
 
@@ -264,11 +244,7 @@ __global__ __launch_bounds__(TH) void sim_resident_kernel(PanelDev P, ResRun r, 
 #pragma unroll
       for (int k = 0; k < NA; ++k) {
         const int i0 = base + k * TH + tid;
-#ifdef AIY_DIAG_QUAD_DUP
-        const int i = (i0 < cnt ? i0 : cnt - 1) & ~3;   // diagnostic build only: 4 lanes, one agent
-#else
         const int i = i0 < cnt ? i0 : cnt - 1;                                            // tail lanes: dummy work
-#endif
         ln[k] = L[i];
         m[k] = Rnow * A[i] + Wnow * (s_lvl[ln[k]] * 1.0);                                 // AS:1283
         cell[k] = (2 * ln[k] + Mrkv) * n_J + jc;                                          // employed (Urate = 0)
@@ -313,11 +289,7 @@ __global__ __launch_bounds__(TH) void sim_resident_kernel(PanelDev P, ResRun r, 
 #pragma unroll
       for (int k = 0; k < NA; ++k) {
         const int i = base + k * TH + tid;
-#ifdef AIY_DIAG_QUAD_DUP
-        if (i < cnt && (i & 3) == 0) {
-#else
         if (i < cnt) {
-#endif
           const double an = m[k] - c[k];                                                  // AS:1415
           A[i] = an;
           local += an;
@@ -343,21 +315,8 @@ __global__ __launch_bounds__(TH) void sim_resident_kernel(PanelDev P, ResRun r, 
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // ---- 3. next period's labour draws overlap the exchange (waves 1..; wave 0 sweeps) ----
-#ifndef AIY_DRAW_MODE
-#define AIY_DRAW_MODE 2
-#endif
-    if (p + 1 < r.n_periods || (flags & kResDrawNext)) {
-#if AIY_DRAW_MODE == 0   // every wave draws, wave 0 then sweeps
-      draw_slice<kDrawGroup>(r, offset, L, start, cnt, t + 1, s_cdf, n_lab, tid, TH);
-#elif AIY_DRAW_MODE == 1   // wave 4 takes wave 0's pairs
-      if (tid >= kWave) {
-        draw_slice<kDrawGroup>(r, offset, L, start, cnt, t + 1, s_cdf, n_lab, tid, TH);
-        if (tid >= 4 * kWave && tid < 5 * kWave)
-          draw_slice<kDrawGroup>(r, offset, L, start, cnt, t + 1, s_cdf, n_lab, tid - 4 * kWave, TH);
-      }
-#else   // waves 1.. share every pair
-      if (tid >= kWave) draw_slice<kDrawGroup + 1>(r, offset, L, start, cnt, t + 1, s_cdf, n_lab, tid - kWave, TH - kWave);
-#endif
+    if (p + 1 < r.n_periods || (flags & kResDrawNext)) {   // waves 1.. share every pair
+      if (tid >= kWave) draw_slice<kDrawGroup + 1>(r, offset, Slice{L, start, cnt}, t + 1, s_cdf, n_lab, tid - kWave, TH - kWave);
     }
     AIY_PH(2);
     // ---- 4. wave 0 sweeps every workgroup's granules, sums in fixed order, prices (sharded:
@@ -444,13 +403,13 @@ __global__ __launch_bounds__(TH) void sim_resident_kernel(PanelDev P, ResRun r, 
 }
 
 // Workgroup shape (threads per workgroup, agents per lane per pass, record loads) by
-// handle option: 0 -> 512 x 8 quad-cooperative (default: a ~4k-agent slice in ONE pass,
+// shape id (AIY_OPT_RESIDENT_SHAPE, AIY_OPT_RESIDENT_SHAPE_STREAM): 0 -> 512 x 8 quad-cooperative (default: a ~4k-agent slice in ONE pass,
 // 256 VGPRs), 1 -> 1024 x 4 quad-cooperative, 2 -> 512 x 8 per-lane record loads.
 struct ResShape {
   int id, th, na;
 };
-static ResShape res_shape(const aiy_handle* h) {
-  switch (h->res_shape) {
+static ResShape res_shape(int id) {
+  switch (id) {
     case 1: return ResShape{1, 1024, 4};
     case 2: return ResShape{2, 512, 8};
     default: return ResShape{0, 512, 8};
@@ -484,26 +443,29 @@ bool resident_supported(const PanelDev& P) {
   return res_hdr_bytes(P.tab.g.n_cells) <= kResHdrMaxBytes && P.n_M <= kResMaxM;
 }
 
-// Launch the resident kernel for periods [t0, t0 + n_periods) (single rank).
-int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, long long n, double* a, uint8_t* lab,
-                        const double* u, long long u_ld, unsigned long long seed, unsigned ge_iter, int t0,
-                        int n_periods, double* sow, double* hist_A, double* hist_M, hipStream_t st,
-                        long long offset, int flags, long long n_total) {
+// Every instantiation once: [shape][form].
+enum { kFormStream, kFormStreamShard, kFormLds };
+#define AIY_RES_FORMS(TH, NA, QUAD)                                                    \
+  {reinterpret_cast<const void*>(sim_resident_kernel<TH, NA, false, QUAD, false>),     \
+   reinterpret_cast<const void*>(sim_resident_kernel<TH, NA, false, QUAD, true>),      \
+   reinterpret_cast<const void*>(sim_resident_kernel<TH, NA, true, QUAD, true>)}
+static const void* const kResKernels[3][3] = {AIY_RES_FORMS(512, 8, true), AIY_RES_FORMS(1024, 4, true),
+                                              AIY_RES_FORMS(512, 8, false)};
+#undef AIY_RES_FORMS
+
+// Launch the resident kernel for periods [r.t0, r.t0 + r.n_periods).
+int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, ResRun r, hipStream_t st) {
   if (!resident_supported(P)) return fail(h, AIY_ERR_UNSUPPORTED, "resident panel: header table too large");
-  if (!resident_aligned(a, lab))
+  if (!resident_aligned(r.a, r.lab))
     return fail(h, AIY_ERR_ARG, "resident panel: assets must be 16-byte and labour states 2-byte aligned");
-  ResShape sh = res_shape(h);
-  ResGeometry G = res_geometry(h, n, P.tab.g.n_cells, sh);
+  ResShape sh = res_shape(h->res_shape);
+  ResGeometry G = res_geometry(h, r.n, P.tab.g.n_cells, sh);
   if (!G.in_lds && h->res_shape_stream >= 0 && h->res_shape_stream != sh.id) {
     // the HBM-streaming form has its own shape (default 1024 x 4: 4 waves per SIMD hide the
     // streamed agents' latency better, 1 150 vs 1 504 us per period at 1e8 agents,
     // profiles/r05h_panel_shapes.jsonl)
-    ResShape ss = sh;
-    const int keep = h->res_shape;
-    h->res_shape = h->res_shape_stream;
-    ss = res_shape(h);
-    h->res_shape = keep;
-    const ResGeometry Gs = res_geometry(h, n, P.tab.g.n_cells, ss);
+    const ResShape ss = res_shape(h->res_shape_stream);
+    const ResGeometry Gs = res_geometry(h, r.n, P.tab.g.n_cells, ss);
     if (!Gs.in_lds) {
       sh = ss;
       G = Gs;
@@ -512,55 +474,35 @@ int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, 
   const int32_t rc = h->res_sync.reserve(h, kResSyncBytes);
   if (rc) return rc;
   AIY_HIP(h, h->res_timer.ensure());
-  // [shape][in LDS][sharded]
-  const void* kernels[3][2][2] = {
-      {{reinterpret_cast<const void*>(sim_resident_kernel<512, 8, false, true, false>),
-        reinterpret_cast<const void*>(sim_resident_kernel<512, 8, false, true, true>)},
-       {reinterpret_cast<const void*>(sim_resident_kernel<512, 8, true, true, true>),
-        reinterpret_cast<const void*>(sim_resident_kernel<512, 8, true, true, true>)}},
-      {{reinterpret_cast<const void*>(sim_resident_kernel<1024, 4, false, true, false>),
-        reinterpret_cast<const void*>(sim_resident_kernel<1024, 4, false, true, true>)},
-       {reinterpret_cast<const void*>(sim_resident_kernel<1024, 4, true, true, true>),
-        reinterpret_cast<const void*>(sim_resident_kernel<1024, 4, true, true, true>)}},
-      {{reinterpret_cast<const void*>(sim_resident_kernel<512, 8, false, false, false>),
-        reinterpret_cast<const void*>(sim_resident_kernel<512, 8, false, false, true>)},
-       {reinterpret_cast<const void*>(sim_resident_kernel<512, 8, true, false, true>),
-        reinterpret_cast<const void*>(sim_resident_kernel<512, 8, true, false, true>)}}};
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (auto& shape : kernels)
-      for (auto& row : shape)
-        for (const void* k : row)
-          AIY_HIP(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResLdsBudget));
-    attr_set = true;
+  if (!h->res_attr_set) {   // LDS beyond the 64 KiB default, on this handle's device
+    for (auto& shape : kResKernels)
+      for (const void* k : shape)
+        AIY_HIP(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResLdsBudget));
+    h->res_attr_set = true;
   }
-  ResRun r;
-  r.n = n; r.offset = offset; r.chunk = G.chunk; r.a = a; r.lab = lab; r.u = u; r.u_ld = u_ld; r.seed = seed;
-  r.ge_iter = ge_iter; r.t0 = t0; r.n_periods = n_periods; r.sow = sow;
+  r.chunk = G.chunk;
   r.gran = h->res_sync.as<unsigned long long>();
   r.tmo = reinterpret_cast<unsigned*>(h->res_sync.as<char>() + kResGranBytes);
-  r.hist_A = hist_A; r.hist_M = hist_M;
-  r.flags = flags;
-  r.n_total = n_total > 0 ? n_total : n;
+  if (r.n_total <= 0) r.n_total = r.n;
   // granule tags unique over the handle's launches: the slots need zeroing only when the tag
   // counter starts over (the first launch, or after 2^31 periods)
   if (h->res_epoch == 0 || h->res_epoch > 0x7fffffffu) {
     AIY_HIP(h, hipMemsetAsync(h->res_sync.get(), 0, kResSyncBytes, st));
     h->res_epoch = 0;
-  } else if (!(flags & kResKeepTmo)) {
+  } else if (!(r.flags & kResKeepTmo)) {
     AIY_HIP(h, hipMemsetAsync(r.tmo, 0, sizeof(unsigned), st));
   }
   r.ep0 = h->res_epoch;
-  h->res_epoch += (unsigned)n_periods + 1u;
+  h->res_epoch += (unsigned)r.n_periods + 1u;
   PanelDev Pc = P;
   aiy_market mkc = mk;
   void* args[] = {&Pc, &r, &mkc};
-  const bool shard = flags != kResDraw0 || offset != 0;   // any non-single-rank launch
+  const bool shard = r.flags != kResDraw0 || r.offset != 0;   // any non-single-rank launch
   // the LDS-resident form always takes the runtime-flag instantiation: its folded single-rank
   // twin spilled more (124 vs 68 B per lane) and ran configs[1]'s periods at 16.8-16.9 against
   // 15.8-15.9 us (A/B on one box, gpurun_out/s7a_ablegs_*); the streaming form is the reverse
   // (1 004 vs 1 045 us per period at configs[3], r08b_c3ab)
-  const void* fn = kernels[sh.id][G.in_lds ? 1 : 0][(shard || G.in_lds) ? 1 : 0];
+  const void* fn = kResKernels[sh.id][G.in_lds ? kFormLds : shard ? kFormStreamShard : kFormStream];
   // Co-residency of the grid (one workgroup per CU, nb <= CU count) is checked here once
   // against the occupancy query; a plain launch then has the same residency as a
   // cooperative one without its per-launch host cost (MI355X_MICROARCH.md, coop-launch),
@@ -576,11 +518,11 @@ int32_t launch_resident(aiy_handle* h, const PanelDev& P, const aiy_market& mk, 
   }
   // HIP events bracket the single-rank launches (aiy_panel_launch_stats); the sharded per-period
   // launches are timed by the caller's clock
-  const bool timed = !(flags & kResSharded);
+  const bool timed = !(r.flags & kResSharded);
   if (timed) AIY_HIP(h, h->res_timer.begin(st));
   AIY_HIP(h, hipLaunchKernel(fn, dim3(G.nb), dim3(sh.th), args, G.lds, st));
   if (timed) AIY_HIP(h, h->res_timer.end(st));
-  h->res_periods += n_periods;
+  h->res_periods += r.n_periods;
   return AIY_OK;
 }
 

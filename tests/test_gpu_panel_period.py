@@ -55,10 +55,10 @@ def dv(dev, x):
 class Rig:
     """A DevicePanel bound to one family member; every run starts from its own reset."""
 
-    def __init__(self, dev, fam, N, engine, unemployed=False):
+    def __init__(self, dev, fam, N, engine, unemployed=False, agent_offset=0):
         from aiyagari_hark_amd.panel import DevicePanel
         self.dev, self.fam, self.N = dev, fam, N
-        self.p = DevicePanel(N, device=dev, act_T=fam.mrkv_hist.size, engine=engine)
+        self.p = DevicePanel(N, device=dev, agent_offset=agent_offset, act_T=fam.mrkv_hist.size, engine=engine)
         self.p.bind_model(dv(dev, fam.m), dv(dev, fam.c), dv(dev, fam.Mgrid), dv(dev, fam.lvl), dv(dev, fam.cdf),
                           dv(dev, fam.mrkv_hist), PR.MARKET, unemployed=unemployed)
 
@@ -250,7 +250,7 @@ def draw_agents(fam, N, rng):
 @pytest.mark.parametrize("engine", ("grid", "block", "resident"))
 def test_labour_draw_edges(gpu, engine, n_lab):
     """searchsorted(cdf[l], u, 'right') at u on a CDF entry; the resident kernel draws in
-    draw_slice, the others in the lookup loop."""
+    draw_slice, the others in agent_step (csrc/panel_common.h)."""
     from aiyagari_hark_amd import _lib
     fam = PR.Family(n_lab, 2, 17, 6)
     rng = np.random.default_rng([29, n_lab])
@@ -473,6 +473,27 @@ def test_resident_philox_period(gpu):
     out = Rig(gpu, fam, N, "grid").run(a0, lab0, None, sow0, seed=seed, ge_iter=ge)
     u = PX.uniform(ge << 20, np.arange(N, dtype=np.uint64), seed)
     check("resident philox", "resident", out, fam, a0, lab0, u, sow0)
+
+
+def test_single_rank_offset_philox_period(gpu):
+    """One rank whose agents start at global index 2: the Philox draws are those of indices
+    2 + i, so the call runs the per-period kernel (the resident kernel's single-rank forms draw at
+    offset 0) although AIY_OPT_RESIDENT is on and the count is above its threshold."""
+    from aiyagari_hark_amd import _lib
+    N, off, seed, ge = 65539, 2, 77, 3
+    fam, a0, lab0, _, sow0, _ = resident_case(N, 3)
+    h = _lib.handle(gpu.index)
+    prev = h.set_options({_lib.AIY_OPT_RESIDENT: 1})
+    try:
+        before = resident_periods(h)
+        out = Rig(gpu, fam, N, "grid", agent_offset=off).run(a0, lab0, None, sow0, seed=seed, ge_iter=ge)
+        after = resident_periods(h)
+    finally:
+        h.set_options(prev)
+    u = PX.uniform(ge << 20, off + np.arange(N, dtype=np.uint64), seed)
+    assert np.array_equal(out["lab"], H.draw_labor(lab0, u, fam.cdf))
+    check("grid philox offset 2", "grid", out, fam, a0, lab0, u, sow0)
+    assert after == before
 
 
 # ---------------------------------------------------------------------------------------
